@@ -19,10 +19,13 @@ every N so that the per-N values compare:
     and run --pair-workers at a time per GPU, RCCL only for the final gather
     of every pair's blocks (npge_amd/pairs.py) -- strong scaling over the
     fixed pair job; value = all pairs' input bp / time.
-Every line also carries, each timed on its own after the headline:
-"sharded" (N > 1: one set over the ranks; with --mode sharded "replicas"
-instead) and "pairs" (the C4 pair-sharded job at this N), so one SCALE run
-gives all three curves.  (DESIGN.md "Multi-GPU").
+A plain run sets up, warms up, times the K steps and prints the line.  With
+--full the line also carries, each measured on its own after the headline:
+"stage_timeline" (one extra step), "pcie_inclusive" (the upload),
+"cpu_baseline", "sharded" (N > 1: one set over the ranks; with --mode sharded
+"replicas" instead) and "pairs" (the C4 pair-sharded job at this N), so one
+SCALE run gives all three curves.  (DESIGN.md "Multi-GPU").
+--dump-outputs DIR writes what the last timed step computed as DIR/*.npy.
 
 Prints ONE JSON line on rank 0.
 """
@@ -42,6 +45,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also measure what takes runs of its own: the stage "
+                         "timeline (one extra step), the upload (pcie_inclusive), the secondary sharded / "
+                         "replicas and pairs lines and the CPU baselines; without it the run sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the block set the "
+                         "engine holds; --mode pairs: the gathered records) as DIR/<name>.npy, float32/float64, "
+                         "in an order that does not depend on the order the engine lists blocks in; outputs "
+                         "too large are cut to a fixed, seeded sample (dump_blockset, dump_pairs)")
     ap.add_argument("--config", default=None,
                     help="synthetic genome set (npge_amd/synth.py); default C3 = the 17-genome ≥50x target "
                          "config (C4 with --mode pairs)")
@@ -174,10 +187,13 @@ def main():
     comm_ranks = comm.count() if comm is not None else 1
     if args.mode == "pairs":
         line = run_pairs(args, dist, world, rank, local_rank, comm, args.config, args.pairs,
-                         args.steps, args.warmup, baseline=not args.no_cpu_baseline)
+                         args.steps, args.warmup, baseline=args.full and not args.no_cpu_baseline,
+                         dump_dir=args.dump_outputs)
         if rank == 0:
             line["comm_ranks"] = comm_ranks
             line["launcher"] = launcher_name()
+            if not args.full:
+                line.pop("cpu_baseline")
             print(json.dumps(line), flush=True)
         finish(dist, world, comm)
         return
@@ -218,37 +234,43 @@ def main():
 
     if roofline is not None:
         roofline.update(pmc_traffic(dom["name"], args.config))
-    # stage accounting from one extra, untimed step with HIP events at the
-    # stage boundaries (markers cost the GPU time: never in the timed region)
-    stages = job.stage_timeline()
-    stages["ms_per_step"] = round(dt / args.steps * 1e3, 4)
-    if args.anchor_loop:  # (the stage clock splits the DraftPangenome part of the step only)
-        stages["scope"] = "DraftPangenome only: the step's AnchorLoopFast is not split into stages"
+    if args.dump_outputs and rank == 0:  # the last timed step's block set, before anything else runs
+        dump_blockset(args.dump_outputs, blockset_arrays(job.eng), job.eng.hash(), job.eng.rows_digest())
     workload = job.workload_name(args.config)
+    stages = pcie = None
+    if args.full:
+        # stage accounting from one extra, untimed step with HIP events at the
+        # stage boundaries (markers cost the GPU time: never in the timed region)
+        stages = job.stage_timeline()
+        stages["ms_per_step"] = round(dt / args.steps * 1e3, 4)
+        if args.anchor_loop:  # (the stage clock splits the DraftPangenome part of the step only)
+            stages["scope"] = "DraftPangenome only: the step's AnchorLoopFast is not split into stages"
     del job
 
-    # the boundary takes host buffers: npgx_seqset_create's own timings, the
-    # host to_atgcn (excluded, like the CPU side's input conversion) and the
-    # upload proper (one DMA of the text + k_pack: BASELINE.md's "H2D included
-    # on the GPU side"), median of 3; `value` stays HBM-resident (the task's
-    # measurement contract), `pcie_inclusive` adds the upload to every step
-    import statistics
-    hosts, ups = [], []
-    for _ in range(3):
-        ss2 = _capi.SeqSet(seqs, names)
-        h_ms, u_ms = ss2.timings()
-        hosts.append(h_ms)
-        ups.append(u_ms)
-        ss2.close()
-    up = statistics.median(ups) / 1e3
-    step_s = dt / args.steps
-    pcie = {"upload_ms": round(up * 1e3, 3), "host_to_atgcn_ms": round(statistics.median(hosts), 3),
-            "value": round(harness.throughput(bp, 1 if sharded else world, 1, step_s + up) / 1e6, 3),
-            "note": "upload = H2D of the text from pinned staging + k_pack, per step; host to_atgcn excluded"}
+    if args.full:
+        # the boundary takes host buffers: npgx_seqset_create's own timings, the
+        # host to_atgcn (excluded, like the CPU side's input conversion) and the
+        # upload proper (one DMA of the text + k_pack: BASELINE.md's "H2D included
+        # on the GPU side"), median of 3; `value` stays HBM-resident (inputs
+        # uploaded before the timed region), `pcie_inclusive` adds the upload to
+        # every step
+        import statistics
+        hosts, ups = [], []
+        for _ in range(3):
+            ss2 = _capi.SeqSet(seqs, names)
+            h_ms, u_ms = ss2.timings()
+            hosts.append(h_ms)
+            ups.append(u_ms)
+            ss2.close()
+        up = statistics.median(ups) / 1e3
+        step_s = dt / args.steps
+        pcie = {"upload_ms": round(up * 1e3, 3), "host_to_atgcn_ms": round(statistics.median(hosts), 3),
+                "value": round(harness.throughput(bp, 1 if sharded else world, 1, step_s + up) / 1e6, 3),
+                "note": "upload = H2D of the text from pinned staging + k_pack, per step; host to_atgcn excluded"}
 
-    # secondary lines, each in its own timed region after the headline's
+    # secondary lines (--full), each in its own timed region after the headline's
     other = None
-    if world > 1 and not args.no_replicas_line:
+    if args.full and world > 1 and not args.no_replicas_line:
         if sharded:  # the same step in replica mode (every rank its own set, no collective)
             rseed = harness.rank_seed(synth.BASE_SEED, rank, args.config)
             rnames, rseqs = synth.genome_set(args.config, seed=rseed)
@@ -269,7 +291,7 @@ def main():
                       % (world, "library RCCL communicator" if args.dist_backend == "nccl" else args.dist_backend)}
         del rjob, rss
     pairs_line = None
-    if not args.no_pairs_line and args.anchor_loop is False:
+    if args.full and not args.no_pairs_line and args.anchor_loop is False:
         # BASELINE C4's split at every N: genome pairs over the ranks, RCCL gather at the end
         pairs_line = run_pairs(args, dist, world, rank, local_rank, comm, args.pairs_config, args.pairs,
                                min(args.steps, 2), 1, baseline=not args.no_cpu_baseline, cpu_runs=3)
@@ -279,7 +301,7 @@ def main():
                                                      "device_mem_used_gb", "roofline", "cpu_baseline")}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_sample or args.config, args.cpu_runs)
         if args.anchor_loop:  # the CPU leg times DraftPangenome only: not like-for-like
             cpu["workload"] = ("DraftPangenome only (the GPU step adds %s): no speedup ratio implied"
@@ -304,7 +326,8 @@ def main():
             "config": {"workload": workload, "bp_per_rank": bp,
                        "genomes": synth.CONFIGS[args.config][0], "anchor_size": 20,
                        "anchor_fp": 0.1, "max_anchor_fragments": 100000,
-                       "inputs": "resident in HBM before the timed region (upload: pcie_inclusive)",
+                       "inputs": "resident in HBM before the timed region"
+                                 + (" (upload: pcie_inclusive)" if args.full else ""),
                        "timers": "HIP events around the k_align_jobs launches only (NPGX_TIMERS=1: every "
                                  "event is a queue marker that costs the GPU time; per-kernel times of the "
                                  "rest: the rocprofv3 summaries in profiles/)",
@@ -321,8 +344,140 @@ def main():
             ("replicas" if sharded else "sharded"): other,
             "pairs": pairs_line,
         }
+        if not args.full:  # not measured: the line leaves out what only --full fills in
+            for k in ("stage_timeline", "pcie_inclusive", "cpu_baseline", "replicas", "sharded", "pairs"):
+                line.pop(k, None)
         print(json.dumps(line), flush=True)
     finish(dist, world, comm)
+
+
+# --dump-outputs: at most DUMP_FRAGMENTS fragments (6 float64 arrays) and
+# DUMP_ROW_CELLS row cells (float32) are written, 59 MB in all; of a larger
+# output a sample drawn with DUMP_SEED (the same indices whenever the sizes agree)
+DUMP_SEED = 20261019
+DUMP_FRAGMENTS = 1 << 19
+DUMP_ROW_CELLS = 1 << 23
+
+
+def _split64(x):
+    """A 64-bit value as its two 32-bit halves (high, low): exact in float64."""
+    x = int(x)
+    return [float(x >> 32), float(x & 0xffffffff)]
+
+
+def _canonical_order(pair, blk, seq, mn, mx, ori):
+    """-> (perm, block): the fragments sorted inside their block and the blocks
+    by (pair, first fragment, size, last fragment); block[i] is the new number
+    of the block of fragment perm[i].  The engine lists blocks in the order it
+    made them, which carries no meaning (the reference's BlockSet is an
+    unordered set).  Blocks equal in all of these keys (none is expected: they
+    would share two fragments) would keep the engine's order among themselves."""
+    import numpy as np
+    n = len(seq)
+    if n == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    _, gid = np.unique(pair.astype(np.int64) * (1 << 32) + blk.astype(np.int64), return_inverse=True)
+    o1 = np.lexsort((ori, mx, mn, seq, gid))
+    g = gid[o1]
+    first = np.flatnonzero(np.r_[True, g[1:] != g[:-1]])
+    size = np.diff(np.r_[first, n])
+    f, l = o1[first], o1[first + size - 1]
+    by = np.lexsort((ori[l], mx[l], mn[l], seq[l], size, ori[f], mx[f], mn[f], seq[f], pair[f]))
+    number = np.empty(len(first), dtype=np.int64)
+    number[by] = np.arange(len(first))
+    block = np.repeat(number, size)
+    o2 = np.argsort(block, kind="stable")
+    return o1[o2], block[o2]
+
+
+def _save(dump_dir, arrays):
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def blockset_arrays(eng):
+    """The block set a BlockSetEngine holds as numpy arrays, rows included and
+    nothing decoded: (block_start[nb + 1], seq, min, max, ori, row_start[nf + 1],
+    rows as uint8); fragment i's gapped row is rows[row_start[i]:row_start[i + 1]]
+    (empty: no row)."""
+    import ctypes
+    import numpy as np
+    from npge_amd import _capi
+    L, h = _capi.lib(), eng._h
+    nb, nf, rb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _capi.check(L.npgx_blockset_counts(h, ctypes.byref(nb), ctypes.byref(nf), ctypes.byref(rb)))
+    n = max(nf.value, 1)
+    bs = np.zeros(nb.value + 1, dtype=np.int64)
+    seq = np.zeros(n, dtype=np.int32)
+    mn = np.zeros(n, dtype=np.int64)
+    mx = np.zeros(n, dtype=np.int64)
+    ori = np.zeros(n, dtype=np.int8)
+    ro = np.zeros(n + 1, dtype=np.int64)
+    rows = np.zeros(max(rb.value, 1), dtype=np.uint8)
+    _capi.check(L.npgx_blockset_copy(h, _capi.ptr(bs), _capi.ptr(seq), _capi.ptr(mn), _capi.ptr(mx),
+                                     _capi.ptr(ori), _capi.ptr(ro), _capi.ptr(rows)))
+    f = nf.value
+    return bs, seq[:f], mn[:f], mx[:f], ori[:f], ro[:f + 1], rows[:rb.value]
+
+
+def dump_blockset(dump_dir, arrays, blockset_hash, rows_digest):
+    """Writes a block set given as blockset_arrays() with its hash and rows
+    digest: counts (blocks, fragments, row cells), the hash and the digest
+    (each as two 32-bit halves), per fragment its block, sequence, min, max,
+    ori and row length, and the gapped rows' cells (ASCII codes) concatenated
+    in fragment order."""
+    import numpy as np
+    bs, seq, mn, mx, ori, ro, rows = arrays
+    nf = len(seq)
+    blk = np.repeat(np.arange(len(bs) - 1, dtype=np.int64), np.diff(bs))
+    perm, block = _canonical_order(np.zeros(nf, dtype=np.int64), blk, seq.astype(np.int64), mn, mx,
+                                   ori.astype(np.int64))
+    length = np.diff(ro)[perm]
+    start = np.zeros(nf + 1, dtype=np.int64)  # of the canonical concatenation of the rows
+    np.cumsum(length, out=start[1:])
+    cells = int(start[-1])
+    rng = np.random.default_rng(DUMP_SEED)
+    keep = np.arange(nf) if nf <= DUMP_FRAGMENTS else np.sort(rng.choice(nf, DUMP_FRAGMENTS, replace=False))
+    pos = np.arange(cells) if cells <= DUMP_ROW_CELLS else np.sort(rng.integers(0, cells, DUMP_ROW_CELLS))
+    fr = np.searchsorted(start, pos, side="right") - 1
+    src = ro[:-1][perm][fr] + (pos - start[fr])
+    f64 = lambda a: np.asarray(a, dtype=np.float64)
+    _save(dump_dir, {
+        "counts": f64([len(bs) - 1, nf, cells]),
+        "blockset_hash": f64(_split64(blockset_hash)),
+        "rows_digest": f64(_split64(rows_digest)),
+        "frag_block": f64(block[keep]), "frag_seq": f64(seq[perm][keep]), "frag_min": f64(mn[perm][keep]),
+        "frag_max": f64(mx[perm][keep]), "frag_ori": f64(ori[perm][keep]), "frag_row_length": f64(length[keep]),
+        "rows": rows[src].astype(np.float32)})
+
+
+def dump_pairs(dump_dir, records, summary):
+    """Writes the gathered records of the pair job (npge_amd/pairs.py): per pair
+    (pair, blocks, block-set hash and rows digest as 32-bit halves), and per
+    fragment its pair, block, sequence of the pair, min, max and ori."""
+    import numpy as np
+    from npge_amd import pairs
+    r = np.asarray(records, dtype=np.uint64).reshape(-1, 2)
+    u, i64 = np.uint64, (lambda a: a.astype(np.int64))
+    w0, w1 = r[:, 0], r[:, 1]
+    pair, blk = i64(w0 >> u(44)), i64((w0 >> u(12)) & u((1 << pairs.BLOCK_BITS) - 1))
+    seq, ori = i64((w0 >> u(1)) & u((1 << pairs.SEQ_BITS) - 1)), np.where(i64(w0 & u(1)) > 0, 1, -1)
+    mn, mx = i64(w1 >> u(32)), i64(w1 & u(0xffffffff))
+    perm, block = _canonical_order(pair, blk, seq, mn, mx, ori)
+    nf = len(perm)
+    rng = np.random.default_rng(DUMP_SEED)
+    keep = np.arange(nf) if nf <= DUMP_FRAGMENTS else np.sort(rng.choice(nf, DUMP_FRAGMENTS, replace=False))
+    s = np.asarray(summary, dtype=np.uint64).reshape(-1, pairs.SUMMARY_WORDS)
+    s = s[np.argsort(s[:, 0] >> np.uint64(32), kind="stable")]
+    half = lambda a: [(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xffffffff)).astype(np.float64)]
+    f64 = lambda a: np.asarray(a, dtype=np.float64)
+    _save(dump_dir, {
+        "counts": f64([len(s), nf]),
+        "pair_summary": np.stack(half(s[:, 0]) + half(s[:, 1]) + half(s[:, 2]), axis=1),
+        "frag_pair": f64(pair[perm][keep]), "frag_block": f64(block[keep]), "frag_seq": f64(seq[perm][keep]),
+        "frag_min": f64(mn[perm][keep]), "frag_max": f64(mx[perm][keep]), "frag_ori": f64(ori[perm][keep])})
 
 
 def finish(dist, world, comm):
@@ -334,11 +489,13 @@ def finish(dist, world, comm):
         dist.destroy_process_group()
 
 
-def run_pairs(args, dist, world, rank, local_rank, comm, config, n_pairs, steps, warmup, baseline, cpu_runs=None):
+def run_pairs(args, dist, world, rank, local_rank, comm, config, n_pairs, steps, warmup, baseline, cpu_runs=None,
+              dump_dir=None):
     """The pair-sharded job (npge_amd/pairs.py, BASELINE C4's split).  One step =
     every pair of the set through DraftPangenome once (the rank's share,
     --pair-workers at a time) + the final all-gather of every pair's blocks
-    over `comm`.  Returns rank 0's line (None on other ranks)."""
+    over `comm`.  Returns rank 0's line (None on other ranks).  dump_dir: rank 0
+    writes the last step's gathered records there (dump_pairs)."""
     import gc
     import torch
     from npge_amd import harness, pairs, synth
@@ -357,6 +514,8 @@ def run_pairs(args, dist, world, rank, local_rank, comm, config, n_pairs, steps,
     set_bp = synth.total_bp(seqs)             # the genome set itself (each genome is in G - 1 pairs)
     agg = {k["name"]: k for k in job.kernel_times()}  # each pair's own times, taken right after it ran
     mem = round((lambda f: (f[1] - f[0]) / 2**30)(torch.cuda.mem_get_info()), 2)
+    if dump_dir and rank == 0:
+        dump_pairs(dump_dir, job.records, job.summary)
     del job
     gc.collect()
     kern = [k for k in agg.values() if not k["name"].endswith("_allreduce")]

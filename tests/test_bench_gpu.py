@@ -2,7 +2,7 @@
 torch.distributed.run with the gloo backend (rehearsal of the driver's RCCL
 runs; ranks share the GPU), replicas, sharded and pairs modes.  Checks the
 JSON contract fields, that the sharded line reports one set's bp, and the
-secondary lines (one set sharded / replicas, the pair-sharded job)."""
+secondary lines of --full (one set sharded / replicas, the pair-sharded job)."""
 import json
 import os
 import socket
@@ -27,7 +27,7 @@ def _port():
 def test_bench_two_ranks_gloo(mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
-           "--steps", "1", "--warmup", "1", "--config", "small", "--mode", mode,
+           "--steps", "1", "--warmup", "1", "--config", "small", "--mode", mode, "--full",
            "--dist-backend", "gloo", "--no-cpu-baseline", "--pairs-config", "small", "--pair-workers", "2"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -13,7 +13,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 for rep in 1 2; do
   for v in "$VA" "$VB"; do
-    env $VAR=$v timeout -k 10 300 python bench.py --no-cpu-baseline --no-pairs-line "$@" > $O/ab_${VAR}_${v}_${SFX}_$rep.log 2>&1 || { tail -5 $O/ab_${VAR}_${v}_${SFX}_$rep.log; exit 1; }
+    env $VAR=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-pairs-line "$@" > $O/ab_${VAR}_${v}_${SFX}_$rep.log 2>&1 || { tail -5 $O/ab_${VAR}_${v}_${SFX}_$rep.log; exit 1; }
     python - "$O/ab_${VAR}_${v}_${SFX}_$rep.log" "$VAR=$v" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

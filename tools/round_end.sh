@@ -22,17 +22,17 @@ if [ "$PART" = tests ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
   tail -1 $O/smoke.log
   step bench_c3
-  timeout -k 10 600 python bench.py > $O/bench_c3.log 2>&1 || { tail -5 $O/bench_c3.log; exit 1; }
+  timeout -k 10 600 python bench.py --full > $O/bench_c3.log 2>&1 || { tail -5 $O/bench_c3.log; exit 1; }
   tail -1 $O/bench_c3.log | cut -c1-300
 else
   for cfg in C2 C4 C5 R3; do
     step bench_$cfg
-    timeout -k 10 300 python bench.py --config $cfg --steps 5 --warmup 1 --no-cpu-baseline --no-pairs-line > $O/bench_$cfg.log 2>&1 || { tail -5 $O/bench_$cfg.log; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $cfg --steps 5 --warmup 1 --no-cpu-baseline --no-pairs-line > $O/bench_$cfg.log 2>&1 || { tail -5 $O/bench_$cfg.log; exit 1; }
     tail -1 $O/bench_$cfg.log | cut -c1-200
   done
   for cfg in C3 C4; do
     step bench_${cfg}_alf
-    timeout -k 10 300 python bench.py --config $cfg --anchor-loop --steps 3 --warmup 1 --no-cpu-baseline --no-pairs-line > $O/bench_${cfg}_alf.log 2>&1 || { tail -5 $O/bench_${cfg}_alf.log; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $cfg --anchor-loop --steps 3 --warmup 1 --no-cpu-baseline --no-pairs-line > $O/bench_${cfg}_alf.log 2>&1 || { tail -5 $O/bench_${cfg}_alf.log; exit 1; }
     tail -1 $O/bench_${cfg}_alf.log | cut -c1-200
   done
   step bench_dp

@@ -14,6 +14,6 @@ step smoke
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 step bench
-timeout -k 10 600 python bench.py > $O/bench_c3.log 2>&1 || { tail -5 $O/bench_c3.log; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_c3.log 2>&1 || { tail -5 $O/bench_c3.log; exit 1; }
 tail -1 $O/bench_c3.log | cut -c1-400
 step done

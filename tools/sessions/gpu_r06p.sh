@@ -21,7 +21,7 @@ timeout -k 10 1000 tools/ab_bench.sh libnpge_amd_sw4.so 2 --mode pairs --config 
 cat $O/ab_pairs_sw4.txt | cut -c1-200
 for cfg in C2 C3; do
   step "bench $cfg"
-  timeout -k 10 300 python bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-pairs-line > $O/bench_$cfg.log 2>&1 || { tail -5 $O/bench_$cfg.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-pairs-line > $O/bench_$cfg.log 2>&1 || { tail -5 $O/bench_$cfg.log; exit 1; }
   python -c "import json; d=json.loads(open('$O/bench_$cfg.log').read().strip().splitlines()[-1]); print('$cfg', d['ms_per_step'], d['stage_timeline']['ms'])"
 done
 step done

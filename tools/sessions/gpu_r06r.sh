@@ -14,7 +14,7 @@ timeout -k 10 900 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 tail -1 $O/pytest.log
 for cfg in C3 C2 C3 C2; do
   step "bench $cfg"
-  timeout -k 10 300 python bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-pairs-line > $O/bench_$cfg.log 2>&1 || { tail -5 $O/bench_$cfg.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-pairs-line > $O/bench_$cfg.log 2>&1 || { tail -5 $O/bench_$cfg.log; exit 1; }
   python -c "import json; d=json.loads(open('$O/bench_$cfg.log').read().strip().splitlines()[-1]); print('$cfg', d['ms_per_step'], d['stage_timeline']['ms'])"
 done
 step "af table slots A/B C3"

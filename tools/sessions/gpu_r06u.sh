@@ -12,7 +12,7 @@ timeout -k 10 900 python -u -m pytest tests/ -x -v -m gpu --timeout 300 --timeou
 tail -1 $O/pytest_gpu.log
 for cfg in C5 C3 C2 R3 C5 C3; do
   step "bench $cfg"
-  timeout -k 10 300 python bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-pairs-line > $O/bench_$cfg.log 2>&1 || { tail -5 $O/bench_$cfg.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-pairs-line > $O/bench_$cfg.log 2>&1 || { tail -5 $O/bench_$cfg.log; exit 1; }
   python -c "import json; d=json.loads(open('$O/bench_$cfg.log').read().strip().splitlines()[-1]); print('$cfg', d['ms_per_step'], d['value'], {k: v for k, v in d['stage_timeline']['ms'].items() if v > 0.5})"
 done
 step done
