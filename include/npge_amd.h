@@ -309,7 +309,9 @@ typedef struct {
     int32_t frame_length;           /* Filter frame-length (FRAME_LENGTH 100) */
     int32_t min_end;                /* Filter min-end (MIN_END 10) */
     int32_t min_block;              /* Filter min-block (2) */
-    int32_t max_block;              /* Filter max-block (-1) */
+    int32_t max_block;              /* Filter max-block (-1); find-subblocks does not look
+                                     * at it (Filter.cpp:176-196): a larger block that is
+                                     * good otherwise comes back as its own one slice */
     int32_t find_subblocks;         /* Filter find-subblocks (1) */
     int64_t min_identity_x1e4;      /* FixEnds / Filter min-identity (MIN_IDENTITY 0.9) */
     npgx_align_options align;       /* aligner used by FragmentsExtender */

@@ -140,3 +140,58 @@ def test_bloom_epochs_same_result(epochs):
         rg = g.find(ss)
         ro = o.run(seqs, names)
         _assert_same(rg, ro, g.used_hashes())
+
+
+def _epochs_both(epochs, fp, repeats=2):
+    """`repeats` find calls on one handle over `tiny` (anchor_size 20, seed 3)
+    in `epochs` Bloom epochs, each against the oracle, the used set included."""
+    from npge_amd import _capi
+    names, seqs = synth.genome_set("tiny")
+    ss = _capi.SeqSet(seqs, names)
+    g = _gpu_af(anchor_size=20, bloom_seed=3, anchor_fp=fp)
+    g.set_opt_value("bloom-epochs", epochs)
+    o = orc.AnchorFinder(anchor_size=20, anchor_fp_x1e4=int(round(float(fp) * 10000)), anchor_similar=True, seed=3)
+    ro = None
+    for _ in range(repeats):
+        rg = g.find(ss)
+        ro = o.run(seqs, names)
+        _assert_same(rg, ro, g.used_hashes())
+    return ro
+
+
+@pytest.mark.parametrize("fp,hashes", [("0.05", 4), ("0.03", 5), ("0.01", 7), ("0.001", 10)])
+@pytest.mark.parametrize("epochs", [2, 7])
+def test_bloom_epochs_hash_counts(epochs, fp, hashes):
+    """Several epochs on both sides of FKB = 4 hash functions: up to 4 the
+    window masks carry the P test and the epoch's bits go straight into P;
+    above, the epoch's bits go into the separate Pn, copied into P after the
+    epoch, and k_found_collect_f reads P."""
+    ro = _epochs_both(epochs, fp)
+    assert ro["hashes"] == hashes
+    assert ro["n_found_frags"] > 0
+
+
+def test_bloom_epochs_unfused_launches():
+    """NPGX_AF_EPOCH_FUSE=0: every epoch as its own first-setter and collect
+    launches (the form every NPGX_TIMERS=2 run takes), with the window masks
+    (fp 0.1, 3 hash functions) and without (fp 0.01, 7).  A fresh process: the
+    switch is read once."""
+    import subprocess
+    import sys
+    import textwrap
+    code = textwrap.dedent('''
+        import os, sys
+        os.environ["NPGX_AF_EPOCH_FUSE"] = "0"
+        sys.path.insert(0, ".")
+        sys.path.insert(0, "tests")
+        from test_anchor_finder_gpu import _epochs_both
+        for fp, hashes in (("0.1", 3), ("0.01", 7)):
+            ro = _epochs_both(3, fp)
+            assert ro["hashes"] == hashes, ro["hashes"]
+            assert ro["n_found_frags"] > 0
+        print("same")
+        ''')
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr
+    assert "same" in out.stdout
