@@ -119,6 +119,10 @@ typedef struct {
     int64_t n_blocks;
     int64_t n_fragments;
     int64_t n_used;         /* size of the persistent used-hash set */
+    /* deferred results (DraftPangenome's device anchors) grouped on the host so
+     * far, over the handle's life; a grouping that npgx_af_stats_get itself
+     * triggers counts from the next call on */
+    int64_t host_regroups;
 } npgx_af_stats;
 
 /* The handle owns the persistent used-hash set (AnchorFinder.cpp:30-35): runs on
@@ -221,6 +225,13 @@ void npgx_align_default_options(npgx_align_options* o);
 int npgx_aligner_create(const npgx_align_options* o, npgx_aligner** out);
 int npgx_align_batch(npgx_aligner* a, const char* rows, const int64_t* row_off,
                      const int32_t* job_row_start, int32_t n_jobs);
+/* The same batch through the asynchronous form the device ExtendLoopFast
+ * uses (both attempts enqueued without a host wait between them; the jobs
+ * that overflow the first are listed and re-run on the device): the same
+ * rows; *n_retried = the jobs the first attempt overflowed.  No job may have
+ * more than 64 non-empty rows. */
+int npgx_align_batch_async(npgx_aligner* a, const char* rows, const int64_t* row_off,
+                           const int32_t* job_row_start, int32_t n_jobs, int32_t* n_retried);
 /* Output of the last batch: job j's aligned rows all have length out_len[j];
  * row r's gapped text is out[out_off[r] .. out_off[r] + out_len[job(r)]). */
 int npgx_align_result_sizes(const npgx_aligner* a, int64_t* total_bytes);

@@ -48,7 +48,7 @@ class AfStats(ctypes.Structure):
                 ("n_collected_raw", ctypes.c_int64), ("n_collected", ctypes.c_int64),
                 ("n_found_frags", ctypes.c_int64), ("n_kept_groups", ctypes.c_int64),
                 ("n_blocks", ctypes.c_int64), ("n_fragments", ctypes.c_int64),
-                ("n_used", ctypes.c_int64)]
+                ("n_used", ctypes.c_int64), ("host_regroups", ctypes.c_int64)]
 
 
 class AlignOptions(ctypes.Structure):
@@ -109,6 +109,8 @@ def lib():
         L.npgx_align_default_options.restype = None
         L.npgx_aligner_create.argtypes = [P(AlignOptions), P(vp)]
         L.npgx_align_batch.argtypes = [vp, vp, vp, vp, i32]
+        if hasattr(L, "npgx_align_batch_async"):  # (NPGX_LIB may name an older build)
+            L.npgx_align_batch_async.argtypes = [vp, vp, vp, vp, i32, P(i32)]
         L.npgx_align_result_sizes.argtypes = [vp, P(i64)]
         L.npgx_align_result_copy.argtypes = [vp, vp, vp, vp]
         L.npgx_align_kernel_times.argtypes = [vp, P(KernelTime), i32, P(i32)]

@@ -58,8 +58,11 @@ class BatchAligner:
         _capi.check(L.npgx_aligner_create(ctypes.byref(o), ctypes.byref(h)))
         self._h = h
 
-    def align(self, jobs):
-        """jobs: list of lists of row strings.  Returns the aligned rows."""
+    def align(self, jobs, asynchronous=False):
+        """jobs: list of lists of row strings.  Returns the aligned rows.
+        asynchronous: through npgx_align_batch_async (the form the device
+        ExtendLoopFast uses); the count of jobs the first attempt overflowed
+        is then left in self.retried."""
         L = _capi.lib()
         rows = [r for job in jobs for r in job]
         data = "".join(rows).encode()
@@ -68,8 +71,14 @@ class BatchAligner:
         jstart = np.zeros(len(jobs) + 1, dtype=np.int32)
         np.cumsum([len(j) for j in jobs], out=jstart[1:])
         buf = ctypes.create_string_buffer(data, max(len(data), 1))
-        _capi.check(L.npgx_align_batch(self._h, ctypes.cast(buf, ctypes.c_void_p), _capi.ptr(off),
-                                       _capi.ptr(jstart), len(jobs)))
+        if asynchronous:
+            nr = ctypes.c_int32(0)
+            _capi.check(L.npgx_align_batch_async(self._h, ctypes.cast(buf, ctypes.c_void_p), _capi.ptr(off),
+                                                 _capi.ptr(jstart), len(jobs), ctypes.byref(nr)))
+            self.retried = nr.value
+        else:
+            _capi.check(L.npgx_align_batch(self._h, ctypes.cast(buf, ctypes.c_void_p), _capi.ptr(off),
+                                           _capi.ptr(jstart), len(jobs)))
         tot = ctypes.c_int64()
         _capi.check(L.npgx_align_result_sizes(self._h, ctypes.byref(tot)))
         out = ctypes.create_string_buffer(max(tot.value, 1))

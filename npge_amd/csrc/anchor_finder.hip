@@ -664,6 +664,9 @@ struct npgx_af {
     std::vector<SeqMeta> p_meta;
     std::vector<int32_t> p_by_rank;
     DevBuf<int32_t> d_by_rank;   // rank -> input index (the device's key -> fragment conversion)
+    std::vector<int32_t> d_by_rank_host;  // what d_by_rank holds (uploaded when the sequence set changes)
+    bool d_by_rank_valid = false;
+    int64_t regroups = 0;  // deferred results grouped on the host (npgx_af_stats.host_regroups)
 
     void ensure_temp(size_t bytes) { temp.ensure(bytes); }
 };
@@ -745,6 +748,7 @@ static void af_group_host(npgx_af* af, const std::vector<uint64_t>& keys, const 
                           int key_bits, int32_t R, const SeqMeta* meta, const int32_t* by_rank, int k,
                           bool add_used);
 static void af_materialize(npgx_af* af);
+static void af_pending_used(npgx_af* af);
 
 static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
     static const bool hdbg = getenv("NPGX_AF_DEBUG") != nullptr;  // host phase times to stderr
@@ -755,7 +759,12 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
     NPGX_HIP(hipSetDevice(af->device));
     hipStream_t st = af->stream;
     const int k = af->opt.anchor_size;
-    af_materialize(af);  // (the used set the last run added to)
+    // a deferred result nobody asked for is dropped; only the used hashes it
+    // owes the set (no npgx_af_clear_used since) are added, never its fragments
+    if (af->pending) {
+        if (af->pending_used) af_pending_used(af);
+        af->pending = false;
+    }
     af->timer.reset();
     af->has_result = false;
     npgx_af_stats& S = af->stats;
@@ -1222,10 +1231,17 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
                 af->p_R = R;
                 af->p_meta.assign(meta.begin(), meta.begin() + R);
                 af->p_by_rank.assign(ss->by_rank.begin(), ss->by_rank.begin() + R);
-                af->d_by_rank.ensure((size_t)std::max<int32_t>(R, 1));
-                int32_t* hb = (int32_t*)af->pinned_dl.ensure((size_t)R / 2 + 2);
-                memcpy(hb, af->p_by_rank.data(), (size_t)R * 4);
-                NPGX_HIP(hipMemcpyAsync(af->d_by_rank.p, hb, (size_t)R * 4, hipMemcpyHostToDevice, st));
+                // the rank table depends only on the sequence set: uploaded when it changes
+                if (!af->d_by_rank_valid || af->d_by_rank_host != af->p_by_rank) {
+                    af->d_by_rank_valid = false;
+                    af->d_by_rank.ensure((size_t)std::max<int32_t>(R, 1));
+                    int32_t* hb = (int32_t*)af->pinned_dl.ensure((size_t)R / 2 + 2);
+                    memcpy(hb, af->p_by_rank.data(), (size_t)R * 4);
+                    NPGX_HIP(hipMemcpyAsync(af->d_by_rank.p, hb, (size_t)R * 4, hipMemcpyHostToDevice, st));
+                    af->d_by_rank_host = af->p_by_rank;
+                    af->d_by_rank_valid = true;
+                }
+                // the caller reads the keys on a stream of its own: they are complete when this returns
                 NPGX_HIP(stream_wait(st));
                 S.n_blocks = S.n_fragments = -1;  // (af_materialize)
                 af->has_result = true;
@@ -1317,10 +1333,8 @@ static void af_group_host(npgx_af* af, const std::vector<uint64_t>& keys, const 
     af->has_result = true;
 }
 
-// the deferred host result of the last run (see npgx_af.defer_host)
-static void af_materialize(npgx_af* af) {
-    if (!af->pending) return;
-    af->pending = false;
+// the deferred run's sorted keys and kept hashes -> host_keys / host_H
+static void af_download_pending(npgx_af* af) {
     hipStream_t st = af->stream;
     NPGX_HIP(hipSetDevice(af->device));
     std::vector<uint64_t>& keys = af->host_keys;
@@ -1334,8 +1348,35 @@ static void af_materialize(npgx_af* af) {
     NPGX_HIP(stream_wait(st));
     memcpy(keys.data(), pk, (size_t)af->p_keep * 8);
     memcpy(Hh.data(), pk + af->p_keep, (size_t)af->p_G * 8);
-    af_group_host(af, keys, Hh, af->p_key_bits, af->p_R, af->p_meta.data(), af->p_by_rank.data(), af->p_k,
-                  af->pending_used);
+}
+
+// the deferred host result of the last run (see npgx_af.defer_host)
+static void af_materialize(npgx_af* af) {
+    if (!af->pending) return;
+    af->pending = false;
+    af_download_pending(af);
+    af->regroups++;
+    af_group_host(af, af->host_keys, af->host_H, af->p_key_bits, af->p_R, af->p_meta.data(),
+                  af->p_by_rank.data(), af->p_k, af->pending_used);
+}
+
+// the used hashes of a deferred result that is not asked for (a second run
+// without npgx_af_clear_used): pass 1 of af_group_host alone, the hash of
+// every group after the first; no fragments
+static void af_pending_used(npgx_af* af) {
+    af_download_pending(af);
+    const std::vector<uint64_t>& keys = af->host_keys;
+    const std::vector<uint64_t>& Hh = af->host_H;
+    const int key_bits = af->p_key_bits;
+    const bool sort_used = !af->used.empty();
+    const size_t nk = keys.size(), n0 = af->used.size();
+    for (size_t i = 1; i < nk; i++) {
+        const uint64_t idx = keys[i] >> key_bits;
+        if (idx != (keys[i - 1] >> key_bits)) af->used.push_back(Hh[idx]);
+    }
+    if (sort_used) std::sort(af->used.begin(), af->used.end());
+    if (af->used.size() != n0) af->used_dirty = true;
+    af->pending_used = false;
 }
 
 void af_set_defer(npgx_af* af, bool on) { af->defer_host = on; }
@@ -1415,8 +1456,10 @@ int npgx_af_run_sharded(npgx_af* af, const npgx_seqset* s, const npgx_comm* comm
 int npgx_af_stats_get(const npgx_af* af, npgx_af_stats* out) {
     return guard([&] {
         NPGX_REQUIRE(af && out, NPGX_ERR_ARG, "null argument");
+        const int64_t regroups = af->regroups;  // (not the grouping this call itself may need)
         af_materialize(const_cast<npgx_af*>(af));
         *out = af->stats;
+        out->host_regroups = regroups;
     });
 }
 

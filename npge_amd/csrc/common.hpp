@@ -330,9 +330,10 @@ class HostPool {
 // taking the next index; the first exception is rethrown
 void heavy_for(size_t n, int64_t work, const std::function<void(size_t)>& f);
 
-// similar_aligner.hip: batched align_seqs (results in the aligner's host buffers)
+// similar_aligner.hip: batched align_seqs (results in the aligner's host buffers);
+// n_retried non-null: through align_device's async mode (AlignAsync below)
 void align_batch(npgx_aligner* al, const char* rows, const int64_t* row_off,
-                 const int32_t* job_row_start, int32_t n_jobs);
+                 const int32_t* job_row_start, int32_t n_jobs, int32_t* n_retried = nullptr);
 // device-resident batch: results stay in the aligner's scratch
 struct AlignResult {
     std::vector<int32_t> len;          // alignment length per job

@@ -155,6 +155,13 @@ struct SaArgs {
     unsigned int* sctr;
     int32_t* qseg;
     int32_t* qsub;
+    // align_device's async mode (out null otherwise): the wave that makes a
+    // job's status final writes its result or lists it for the re-run (job_final)
+    JobRows* out;              // per job: its rows, from the attempt that finished it
+    int32_t* err;              // bit 0: a job failed both attempts
+    uint8_t* retried;          // per job: overflowed the first attempt (zeroed before it)
+    int32_t* order1;           // the first attempt's overflowed jobs: the re-run's queue
+    int32_t* ctr1;             // ... their count (zeroed before the first attempt)
     const int32_t* rq;         // k_align_sub's retry launch: the failed sub-jobs (count in counters[5])
     int2* ftasks;
     unsigned char* post_area;  // k_split_post's global work areas (SaSplit.post)
@@ -178,6 +185,23 @@ struct SaArgs {
     int32_t cap_splits, cap_segs;
     int64_t cap_tgt, cap_find, cap_pool;
 };
+
+// align_device's async mode: job j's status is final (0 / 2: done, 1:
+// overflowed; 3, deferred, is not final) -- called by the one lane that wrote
+// it.  A job the first attempt overflowed joins the re-run's queue; any other
+// gets its rows' record (B of its A|B|C scratch, or A for status 2) from this
+// attempt's job table and scratch, and one that fails the re-run too sets err.
+__device__ __forceinline__ void job_final(const SaArgs& a, int j, const SaJob& job, int status, int len) {
+    if (!a.out) return;
+    if (status == 1 && !a.n_jobs_dev) {  // (n_jobs_dev: the re-run)
+        a.retried[j] = 1;
+        a.order1[atomicAdd(a.ctr1, 1)] = j;
+        return;
+    }
+    if (status != 0 && status != 2) atomicOr(a.err, 1);
+    a.out[j] = JobRows{(const char*)(a.scratch + job.scratch + (status == 2 ? 0 : (int64_t)job.n * job.cap)),
+                       job.cap, len};
+}
 
 // number of columns c in [c0, c1) identical over all rows (score_of :416-426)
 __device__ int count_equal_cols(const WaveCtx& w, const char* buf, int cap, int c0, int c1,
@@ -917,6 +941,9 @@ template <bool LONG, int W>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_align_sub(SaArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long lds_u64[];
     const int lane = threadIdx.x;
+    // the retry launch is nearly always empty: nothing to set up then (uniform
+    // over the grid; slot_epoch keeps the earlier launches' highest epoch)
+    if (a.rq != nullptr && a.counters[5] == 0u) return;
     SlotEnv e = slot_env(a, lds_u64);
     uint32_t epoch = next_epoch(a), lepoch = 0;
     const unsigned int n_sub = (unsigned int)a.alloc[1];
@@ -1104,6 +1131,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
         if (lane == 0) {
             a.job_len[j] = ovf ? why : L;
             a.job_status[j] = ovf ? 1 : 0;
+            job_final(a, j, job, ovf ? 1 : 0, ovf ? why : L);
         }
         epoch = pr.epoch;
         lepoch = pr.lepoch;
@@ -1546,7 +1574,15 @@ __device__ int regions_block(G* gm, int nw, int L, int wf, int min_length, long 
 // (its rows gap-filtered and reversed into C by k_sub_rows); k_fin_copy /
 // k_align_finish assemble B and run realing_end.  A chain that overflowed or
 // does not fit marks the job for the whole-job re-run (status 1).
-static constexpr int CHAIN_PART = 8192;  // output columns per k_chain_copy workgroup
+// output columns per k_chain_copy workgroup: a part spans one or two chain
+// elements (segments of a few hundred columns), so that a workgroup's chain of
+// dependent loads (element -> segment -> rows) is that short and a job's chain
+// is copied by many workgroups at once.  SA_CHAIN_PART: another value for an
+// A/B build.
+#ifndef SA_CHAIN_PART
+#define SA_CHAIN_PART 512
+#endif
+static constexpr int CHAIN_PART = SA_CHAIN_PART;
 
 __device__ __forceinline__ unsigned long long* split_bits(const SaArgs& a, const SaSplit& sp, int s) {
     return sp.post >= 0 ? (unsigned long long*)(a.post_area + sp.post) : a.chain_bits + a.bits_off[s];
@@ -1654,11 +1690,19 @@ __global__ __launch_bounds__(POST_THREADS) void k_chain_copy(SaArgs a, int n_spl
             int lo_b = 0, hi_b = min(4, ce - c);  // this part's columns only
             if (d0 + c < c0) lo_b = c0 - (d0 + c);
             char* d = A + d0 + c;
+            // four columns of this part at an aligned place of every row: one
+            // dword store per row; bytes at the ragged ends and where the
+            // element's place in A is not a multiple of four
+            const bool whole = lo_b == 0 && hi_b == 4 && (((uintptr_t)d | (uintptr_t)cap) & 3) == 0;
             const uint32_t diff = rows_dwords(src + c, (size_t)g.cap, n, x0, [&](int r, uint32_t x) {
                 char* dr = A + (size_t)r * cap + d0 + c;
-                for (int q = lo_b; q < hi_b; q++) dr[q] = (char)(x >> (8 * q));
+                if (whole) *(uint32_t*)dr = x;
+                else
+                    for (int q = lo_b; q < hi_b; q++) dr[q] = (char)(x >> (8 * q));
             });
-            for (int q = lo_b; q < hi_b; q++) d[q] = (char)(x0 >> (8 * q));
+            if (whole) *(uint32_t*)d = x0;
+            else
+                for (int q = lo_b; q < hi_b; q++) d[q] = (char)(x0 >> (8 * q));
             unsigned long long m0 = 0, m1 = 0;
             const int col0 = d0 + c, w0 = col0 >> 6;
             for (int q = lo_b; q < hi_b; q++)
@@ -1722,6 +1766,7 @@ __device__ void split_post_body(const SaArgs& a, const SaSplit& sp, G* gm, long 
         if (tid == 0) {
             a.job_len[j] = ps.fail ? -(200 + ps.fail) : -21;
             a.job_status[j] = 1;
+            job_final(a, j, job, 1, a.job_len[j]);
         }
         return;
     }
@@ -1731,6 +1776,7 @@ __device__ void split_post_body(const SaArgs& a, const SaSplit& sp, G* gm, long 
         if (tid == 0) {
             a.job_len[j] = -22;
             a.job_status[j] = 1;
+            job_final(a, j, job, 1, -22);
         }
         return;
     }
@@ -1805,6 +1851,7 @@ __device__ void split_post_body(const SaArgs& a, const SaSplit& sp, G* gm, long 
         if (tid == 0) {
             a.job_len[j] = -23;
             a.job_status[j] = 1;
+            job_final(a, j, job, 1, -23);
         }
         return;
     }
@@ -1949,20 +1996,30 @@ __global__ __launch_bounds__(POST_THREADS) void k_sub_post(SaArgs a, int first, 
         const SaSub d = a.subs[sp.sub];
         const int n = a.jobs[d.job].n;
         __syncthreads();
+        // the segment results in parallel into LDS (the walk below would wait
+        // for one dependent global load per chain element): pcols / pdst hold
+        // them by segment until the walk overwrites the entries it has passed
+        // (np <= k) with the chain's
+        for (int k = tid; k < sp.K; k += POST_THREADS) {
+            const int4 r = a.seg_res[sp.seg0 + k];
+            pcols[k] = r.y;
+            pdst[k] = r.z ? -1 : r.x;
+        }
+        __syncthreads();
         if (tid == 0) {
             int k = 0, col = 0, np = 0, fail = 0;
             while (k < sp.K) {
-                const int4 r = a.seg_res[sp.seg0 + k];
-                if (r.x <= k || r.z || col + r.y > d.out_cap) {
+                const int nxt = pdst[k], cols = pcols[k];
+                if (nxt <= k || col + cols > d.out_cap) {  // (an overflowed segment: next -1)
                     fail = 1;
                     break;
                 }
                 pk[np] = sp.seg0 + k;
-                pcols[np] = r.y;
+                pcols[np] = cols;
                 pdst[np] = col;
                 np++;
-                col += r.y;
-                k = r.x;
+                col += cols;
+                k = nxt;
             }
             s_np = np;
             s_L = col;
@@ -1978,18 +2035,28 @@ __global__ __launch_bounds__(POST_THREADS) void k_sub_post(SaArgs a, int first, 
         }
         char* out = (char*)(a.pool + d.out_off + 256);
         int same = 0;
-        for (int p = 0; p < s_np; p++) {
+        // a chain element per wave at a time (a segment is a few hundred
+        // columns: one or two dwords a lane), so that the elements' dependent
+        // loads (segment -> rows) run side by side
+        for (int p = tid >> 6; p < s_np; p += POST_THREADS / 64) {
             const SaSeg g = a.segs[pk[p]];
             const char* src = (const char*)(a.seg_pool + g.out);
             const int cols = pcols[p], d0 = pdst[p];
-            for (int c = 4 * tid; c < cols; c += 4 * POST_THREADS) {
+            for (int c = 4 * (tid & 63); c < cols; c += 4 * 64) {
                 const int nb = min(4, cols - c);
                 const uint32_t x0 = *(const uint32_t*)(src + c);
+                char* d0p = out + d0 + c;
+                // dword stores where every row's place is aligned, bytes elsewhere
+                const bool whole = nb == 4 && (((uintptr_t)d0p | (uintptr_t)d.out_cap) & 3) == 0;
                 const uint32_t diff = rows_dwords(src + c, (size_t)g.cap, n, x0, [&](int r, uint32_t x) {
                     char* dr = out + (size_t)r * d.out_cap + d0 + c;
-                    for (int b = 0; b < nb; b++) dr[b] = (char)(x >> (8 * b));
+                    if (whole) *(uint32_t*)dr = x;
+                    else
+                        for (int b = 0; b < nb; b++) dr[b] = (char)(x >> (8 * b));
                 });
-                for (int b = 0; b < nb; b++) out[d0 + c + b] = (char)(x0 >> (8 * b));
+                if (whole) *(uint32_t*)d0p = x0;
+                else
+                    for (int b = 0; b < nb; b++) d0p[b] = (char)(x0 >> (8 * b));
                 for (int b = 0; b < nb; b++) same += !((diff >> (8 * b)) & 0xFFu);
             }
         }
@@ -2098,6 +2165,9 @@ template <bool LONG, int W>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_align_jobs(SaArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long lds_u64[];
     const int lane = threadIdx.x;
+    // the re-run of the async mode is nearly always empty: nothing to set up
+    // then (uniform over the grid; slot_epoch keeps the first attempt's epoch)
+    if (a.n_jobs_dev && *a.n_jobs_dev == 0) return;
     SlotEnv e = slot_env(a, lds_u64);
     Slot& S = e.S;
     char* stage = e.stage;
@@ -2183,6 +2253,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_
             if (lane == 0) {
                 a.job_len[j] = 0;
                 a.job_status[j] = 0;
+                job_final(a, j, job, 0, 0);
             }
             continue;
         }
@@ -2470,6 +2541,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_
         if (lane == 0) {
             a.job_len[j] = ovf ? -30 : L;
             a.job_status[j] = ovf ? 1 : deferred ? 3 : (B == A ? 2 : 0);  // 2: the rows are in A, 3: deferred
+            if (ovf || !deferred) job_final(a, j, job, ovf ? 1 : (B == A ? 2 : 0), ovf ? -30 : L);
         }
         if (lane == 0 && a.job_stats) {  // only when the statistics are wanted
             int64_t* js = a.job_stats + (size_t)j * NPGX_JOB_STATS;
@@ -2549,32 +2621,6 @@ __global__ void k_scatter(const unsigned char* __restrict__ blob, int n_ops) {
         unsigned char* d = (unsigned char*)op.dst;
         for (int64_t i = t; i < op.bytes; i += step) d[i] = op.src < 0 ? 0 : blob[op.src + i];
     }
-}
-
-// align_device's async mode: the jobs the first attempt overflowed (status
-// 1) listed for the re-run at the proven bound
-__global__ void k_retry_list(const int32_t* __restrict__ status, int32_t n, int32_t* __restrict__ order,
-                             int32_t* __restrict__ count, uint8_t* __restrict__ retried) {
-    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const bool r = status[j] == 1;
-    retried[j] = r;
-    if (r) order[atomicAdd(count, 1)] = j;
-}
-// ... and every job's rows (B of its A|B|C scratch, or A for status 2) from
-// the attempt that finished it
-__global__ void k_job_rows(const SaJob* __restrict__ jobs0, const SaJob* __restrict__ jobs1,
-                           const uint8_t* __restrict__ retried, const int32_t* __restrict__ status,
-                           const int32_t* __restrict__ len, int32_t n, const unsigned char* scratch0,
-                           const unsigned char* scratch1, JobRows* __restrict__ out, int32_t* __restrict__ err) {
-    const int32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const bool r = retried[j];
-    const SaJob J = r ? jobs1[j] : jobs0[j];
-    const int32_t st = status[j];
-    if (st != 0 && st != 2) atomicOr(err, 1);
-    out[j] = JobRows{(const char*)((r ? scratch1 : scratch0) + J.scratch + (st == 2 ? 0 : (int64_t)J.n * J.cap)),
-                     J.cap, len[j]};
 }
 
 int weight_factor(int64_t min_identity_x1e4) {
@@ -2687,6 +2733,10 @@ struct npgx_aligner {
     // bytes the per-slot scratch of one launch may take (NPGX_SLOT_BUDGET_MB;
     // default 16 GiB: allocating much more costs seconds on first use)
     int64_t slot_budget = 0;
+    // NPGX_TEST_FIRST_CAP=c (tests): the first attempt's rooms hold the longest
+    // row + c columns at most, so that alignments with more insertions overflow
+    // it and take the re-run at the proven bound (0: off)
+    int test_first_cap = 0;
     std::vector<SaSplit> h_splits;
     std::vector<SaSeg> h_segs;
     std::vector<int2> h_ftasks;
@@ -2727,6 +2777,7 @@ struct npgx_aligner {
     DevBuf<SaJob> d_jobs1;
     DevBuf<int32_t> d_order1, d_ctr1;
     DevBuf<uint8_t> d_retried;
+    DevBuf<unsigned char> d_async;  // npgx_align_batch_async: the jobs' records, err and epoch words
 };
 
 namespace npgx {
@@ -2816,6 +2867,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         // first attempt: 2*max+64 columns (the proven bound is the sum of lengths)
         int64_t cap = std::min<int64_t>(sum, 2ll * mx + 64);
         if (o.aligner_type == 1) cap = mx;
+        if (al->test_first_cap > 0) cap = std::min<int64_t>(cap, (int64_t)mx + al->test_first_cap);
         J.cap = (int32_t)((std::max<int64_t>(cap, 1) + 15) & ~15ll);
         J.scratch = scratch;
         scratch += (3ll * n * J.cap + 255) & ~255ll;
@@ -3349,6 +3401,11 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         A.qseg = nullptr;
         A.qsub = nullptr;
         A.rq = nullptr;
+        A.out = as ? as->out : nullptr;
+        A.err = as ? as->err : nullptr;
+        A.retried = as ? al->d_retried.p : nullptr;
+        A.order1 = as ? al->d_order1.p : nullptr;
+        A.ctr1 = as ? al->d_ctr1.p : nullptr;
         A.ftasks = nullptr;
         A.split_len = o.aligner_type == 0 ? al->split : 0;
         A.twin_rows = nullptr;
@@ -3467,6 +3524,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         if (as) {
             put(al->d_jobs1.p, al->h_jobs1.data(), al->h_jobs1.size() * sizeof(SaJob));
             zero(al->d_ctr1.p, 8);
+            zero(al->d_retried.p, jobs.size());
         }
         flush();
         size_t ti = al->timer.begin(attempt == 0 ? "align_jobs" : "align_jobs_retry", st,
@@ -3591,6 +3649,10 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                 fprintf(stderr, "split job %d n=%d K=%d maxlen=%d valid_states=%d hits=%d ovf=%d chain %s\n", sp.job,
                         n, sp.K, jmax[sp.job], valid, hits, ovf, chain.c_str());
             }
+            // per job, when its own walk or its last segment ended in k_align_jobs
+            // (wall clock; the sub-job launch below sets its sub-jobs beside it)
+            std::vector<int64_t> walk_end;
+            int64_t crit_t0 = INT64_MAX;
             if (al->want_stats) {  // the slowest segments (wall clock at 100 MHz)
                 std::vector<int64_t> sw(2 * segs.size());
                 NPGX_HIP(hipMemcpy(sw.data(), al->d_seg_wall.p, sw.size() * 8, hipMemcpyDeviceToHost));
@@ -3608,9 +3670,12 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                 NPGX_HIP(hipMemcpy(js.data(), al->d_job_stats.p, js.size() * 8, hipMemcpyDeviceToHost));
                 int64_t t0 = INT64_MAX, se = 0, je = 0, jd = 0;
                 int jslow = -1;
+                walk_end.assign(n_jobs, 0);
                 for (size_t q = 0; q < segs.size(); q++) {
                     t0 = std::min(t0, sw[2 * q]);
                     se = std::max(se, sw[2 * q + 1]);
+                    int64_t& we = walk_end[splits[segs[q].split].job];
+                    we = std::max(we, sw[2 * q + 1]);
                 }
                 std::vector<uint8_t> was_split(n_jobs, 0);
                 for (const SaSplit& sp2 : splits) was_split[sp2.job] = 1;
@@ -3619,6 +3684,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                     if (was_split[j] || r[11] <= 0 || r[23] <= 0) continue;
                     t0 = std::min(t0, r[11]);
                     je = std::max(je, r[23]);
+                    walk_end[j] = r[23];
                     if (r[23] - r[11] > jd) {
                         jd = r[23] - r[11];
                         jslow = j;
@@ -3632,6 +3698,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                             jslow >= 0 ? jobs[jslow].n : 0,
                             jslow >= 0 ? js[(size_t)jslow * NPGX_JOB_STATS + 8] / 2400.0 : 0.0,
                             jslow >= 0 ? js[(size_t)jslow * NPGX_JOB_STATS + 9] / 2400.0 : 0.0);
+                crit_t0 = t0;
             }
             if (deferring) {  // sub-jobs: count and widths
                 unsigned long long al2[2];
@@ -3665,6 +3732,53 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                             t0 = std::min(t0, segw[2 * q]);
                             send = std::max(send, segw[2 * q + 1]);
                         }
+                    // the pair's critical path by job: each job with sub-jobs, and
+                    // the job that ends either launch (tools/split_stats.py)
+                    if (crit_t0 != INT64_MAX && !walk_end.empty()) {
+                        const size_t nsg = std::min<size_t>(sc2[SC_SEGS], (size_t)A.cap_segs);
+                        const size_t nsp = std::min<size_t>(sc2[SC_SPLITS], (size_t)A.cap_splits);
+                        std::vector<SaSeg> dsg(nsg);
+                        std::vector<SaSplit> dsp(nsp);
+                        if (nsg) NPGX_HIP(hipMemcpy(dsg.data(), al->d_segs.p, nsg * sizeof(SaSeg), hipMemcpyDeviceToHost));
+                        if (nsp) NPGX_HIP(hipMemcpy(dsp.data(), al->d_splits.p, nsp * sizeof(SaSplit), hipMemcpyDeviceToHost));
+                        std::vector<int64_t> s_start(n_jobs, INT64_MAX), s_end(n_jobs, 0);
+                        std::vector<int> s_cnt(n_jobs, 0);
+                        for (size_t q = 0; q < sb.size(); q++) {
+                            const int32_t j = sb[q].job;
+                            if (j < 0 || j >= n_jobs) continue;
+                            s_cnt[j]++;
+                            if (sw2[2 * q] <= 0) continue;  // (split: its segments below; a twin's: no run)
+                            s_start[j] = std::min(s_start[j], sw2[2 * q]);
+                            s_end[j] = std::max(s_end[j], sw2[2 * q + 1]);
+                        }
+                        for (size_t q = segs.size(); q < nsg; q++) {
+                            if (segw[2 * q] <= 0 || dsg[q].split < 0 || (size_t)dsg[q].split >= nsp) continue;
+                            const int32_t sub = dsp[(size_t)dsg[q].split].sub;
+                            if (sub < 0 || (size_t)sub >= sb.size()) continue;
+                            const int32_t j = sb[(size_t)sub].job;
+                            if (j < 0 || j >= n_jobs) continue;
+                            s_start[j] = std::min(s_start[j], segw[2 * q]);
+                            s_end[j] = std::max(s_end[j], segw[2 * q + 1]);
+                        }
+                        int j_jobs = -1, j_subs = -1;
+                        for (int32_t j = 0; j < n_jobs; j++) {
+                            if (walk_end[j] > 0 && (j_jobs < 0 || walk_end[j] > walk_end[j_jobs])) j_jobs = j;
+                            if (s_end[j] > 0 && (j_subs < 0 || s_end[j] > s_end[j_subs])) j_subs = j;
+                        }
+                        for (int32_t j = 0; j < n_jobs; j++)
+                            if (s_end[j] > 0)
+                                fprintf(stderr, "crit job %d: %d rows, %d cols, walk or last segment ends %.1f us; %d "
+                                        "sub-jobs start %.1f us, end %.1f us\n", j, jobs[j].n, jmax[j],
+                                        (walk_end[j] - crit_t0) / 100.0, s_cnt[j], (s_start[j] - crit_t0) / 100.0,
+                                        (s_end[j] - crit_t0) / 100.0);
+                        if (j_jobs >= 0 && j_subs >= 0)
+                            fprintf(stderr, "crit launches: k_align_jobs ends with job %d at %.1f us, k_align_sub with job "
+                                    "%d at %.1f us (%s); job %d's own sub-jobs could have started at %.1f us, the "
+                                    "launch's first started at %.1f us\n", j_jobs, (walk_end[j_jobs] - crit_t0) / 100.0,
+                                    j_subs, (s_end[j_subs] - crit_t0) / 100.0,
+                                    j_jobs == j_subs ? "the same job" : "another job", j_subs,
+                                    (walk_end[j_subs] - crit_t0) / 100.0, (t0 - crit_t0) / 100.0);
+                    }
                     if (t0 != INT64_MAX)
                         fprintf(stderr, "sub launch: %u sub segments end at %.1f us, whole subs at %.1f us; slowest whole "
                                 "sub %d: %.1f us, %d cols, %d rows\n", sc2[SC_SEGS] - (unsigned)segs.size(),
@@ -3684,11 +3798,9 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         pmark(8);
         if (as) {
             // the overflowed jobs again at the proven bound (no splits, no
-            // deferred regions: attempt 1 of the synchronous path), then every
-            // job's rows
-            const unsigned jg = (unsigned)std::max<int64_t>(1, ((int64_t)n_jobs + 255) / 256);
-            hipLaunchKernelGGL(k_retry_list, dim3(jg), dim3(256), 0, st, d_job_status, n_jobs, al->d_order1.p,
-                               al->d_ctr1.p, al->d_retried.p);
+            // deferred regions: attempt 1 of the synchronous path); the waves
+            // that finished the jobs have listed them and written every other
+            // job's rows (job_final), and the re-run's write its own
             SaArgs A1 = A;
             A1.jobs = al->d_jobs1.p;
             A1.order = al->d_order1.p;
@@ -3742,8 +3854,6 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
             else
                 hipLaunchKernelGGL((k_align_jobs<false, SA_WAVES_PER_EU>), dim3((unsigned)slots1), dim3(64), lds_bytes, st, A1);
             al->timer.end(tr, st);
-            hipLaunchKernelGGL(k_job_rows, dim3(jg), dim3(256), 0, st, al->d_jobs.p, al->d_jobs1.p, al->d_retried.p,
-                               d_job_status, d_job_len, n_jobs, scr.p, al->d_scratch2.p, as->out, as->err);
             NPGX_HIP(hipGetLastError());
             NPGX_HIP(hipMemcpyAsync(as->epoch, d_slot_epoch, 4, hipMemcpyDeviceToDevice, st));
             res.len.clear();
@@ -3828,8 +3938,11 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                 pt[3], pt[4], pt[5], pt[6], pt[7], pt[8], pt[9], pt[10]);
 }
 
+// n_retried non-null: through align_device's async mode (the form the device
+// ExtendLoopFast uses, no host wait between the attempts), the count of jobs
+// the first attempt overflowed to *n_retried; same rows either way
 void align_batch(npgx_aligner* al, const char* rows, const int64_t* row_off,
-                 const int32_t* job_row_start, int32_t n_jobs) {
+                 const int32_t* job_row_start, int32_t n_jobs, int32_t* n_retried) {
     NPGX_HIP(hipSetDevice(al->device));
     hipStream_t st = al->stream;
     al->timer.reset();
@@ -3859,7 +3972,36 @@ void align_batch(npgx_aligner* al, const char* rows, const int64_t* row_off,
     std::vector<int32_t> js((size_t)n_jobs + 1);
     for (int32_t j = 0; j <= n_jobs; j++) js[(size_t)j] = (int32_t)(job_row_start[j] - r_base);
     AlignResult res;
-    align_device(al, al->d_rows.p, roff.data(), rlen.data(), js.data(), n_jobs, res);
+    if (n_retried) {
+        const size_t rec = ((size_t)std::max(n_jobs, 1) * sizeof(JobRows) + 15) & ~(size_t)15;
+        al->d_async.ensure(rec + 16);
+        AlignAsync as;
+        as.out = (JobRows*)al->d_async.p;
+        as.err = (int32_t*)(al->d_async.p + rec);
+        as.epoch = (uint32_t*)(al->d_async.p + rec + 4);
+        NPGX_HIP(hipMemsetAsync(al->d_async.p + rec, 0, 16, st));
+        align_device(al, al->d_rows.p, roff.data(), rlen.data(), js.data(), n_jobs, res, &as);
+        std::vector<JobRows> out((size_t)std::max(n_jobs, 1));
+        int32_t tail[2] = {0, 0}, cnt = 0;
+        NPGX_HIP(hipMemcpyAsync(out.data(), as.out, (size_t)n_jobs * sizeof(JobRows), hipMemcpyDeviceToHost, st));
+        NPGX_HIP(hipMemcpyAsync(tail, as.err, 8, hipMemcpyDeviceToHost, st));
+        if (n_jobs) NPGX_HIP(hipMemcpyAsync(&cnt, al->d_ctr1.p, 4, hipMemcpyDeviceToHost, st));
+        NPGX_HIP(stream_wait(st));
+        aligner_note_epoch(al, (uint32_t)tail[1]);
+        al->pinned.reset();
+        NPGX_REQUIRE(tail[0] == 0, NPGX_ERR_STATE, "alignment job overflowed both attempts");
+        *n_retried = cnt;
+        res.len.resize(n_jobs);
+        res.cap.resize(n_jobs);
+        res.bptr.resize(n_jobs);
+        for (int32_t j = 0; j < n_jobs; j++) {
+            res.len[j] = out[(size_t)j].len;
+            res.cap[j] = out[(size_t)j].stride;
+            res.bptr[j] = out[(size_t)j].p;
+        }
+    } else {
+        align_device(al, al->d_rows.p, roff.data(), rlen.data(), js.data(), n_jobs, res);
+    }
     // gather every row (empty rows become all-gap rows), one D2H copy
     std::vector<GatherRow> g((size_t)n_rows);
     int64_t tot = 0;
@@ -3966,6 +4108,8 @@ int npgx_aligner_create(const npgx_align_options* o, npgx_aligner** out) {
         if (ut && *ut) a->utw_rows = std::max(0, atoi(ut));
         const char* utt = getenv("NPGX_UTWIN_TASKS");
         if (utt && *utt) a->utw_max_tasks = std::max(0, atoi(utt));
+        const char* fc = getenv("NPGX_TEST_FIRST_CAP");
+        if (fc && *fc) a->test_first_cap = std::max(0, atoi(fc));
         const char* sb = getenv("NPGX_SLOT_BUDGET_MB");
         if (sb && *sb) {
             a->slot_budget = (int64_t)std::max(1, atoi(sb)) << 20;
@@ -4008,6 +4152,14 @@ int npgx_align_batch(npgx_aligner* a, const char* rows, const int64_t* row_off,
         NPGX_REQUIRE(a && (n_jobs == 0 || (rows && row_off && job_row_start)), NPGX_ERR_ARG,
                      "null argument");
         align_batch(a, rows, row_off, job_row_start, n_jobs);
+    });
+}
+
+int npgx_align_batch_async(npgx_aligner* a, const char* rows, const int64_t* row_off,
+                           const int32_t* job_row_start, int32_t n_jobs, int32_t* n_retried) {
+    return guard([&] {
+        NPGX_REQUIRE(a && row_off && job_row_start && n_retried && (rows || n_jobs == 0), NPGX_ERR_ARG, "null argument");
+        align_batch(a, rows, row_off, job_row_start, n_jobs, n_retried);
     });
 }
 

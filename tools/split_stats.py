@@ -1,11 +1,47 @@
 #!/usr/bin/env python3
 """Diagnostic (GPU box): one DraftPangenome with NPGX_SPLIT_DEBUG=1 -- per split
 aligner job, the sync states found, the segments that reached one, overflows
-and the chain of segments (stderr)."""
+and the chain of segments (stderr).
+
+--critical-path [CONFIG]: the same run in a child process, and of its stderr
+only the late iterations' critical path: for each of the last four aligner
+batches with deferred sub-jobs, per job with sub-jobs when its own walk or its
+last segment ended in k_align_jobs and when its sub-jobs started and ended in
+k_align_sub (microseconds from the batch's first task; the sub-jobs exist once
+the job's chain and regions are known, so their earliest possible start is
+the job's own end plus its k_chain_copy / k_split_post), and which job ends
+either launch."""
 import os
+import subprocess
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+if len(sys.argv) > 1 and sys.argv[1] == "--critical-path":
+    cfg = sys.argv[2] if len(sys.argv) > 2 else "C3"
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), cfg], stderr=subprocess.PIPE,
+                       stdout=subprocess.DEVNULL, text=True)
+    if p.returncode != 0:
+        sys.stderr.write(p.stderr[-2000:])
+        sys.exit(p.returncode)
+    batches, cur = [], []
+    for line in p.stderr.splitlines():
+        if line.startswith(("launch:", "sub launch:", "crit job")):
+            cur.append(line)
+        elif line.startswith("crit launches:"):
+            cur.append(line)
+            batches.append(cur)
+            cur = []
+        elif line.startswith("split job") and cur and not cur[-1].startswith("launch:"):
+            cur = []  # (a batch without deferred sub-jobs)
+    print("%s: %d aligner batches with deferred sub-jobs; the last four:" % (cfg, len(batches)))
+    for i, b in enumerate(batches[-4:]):
+        print("-- batch %d" % (len(batches) - len(batches[-4:]) + i + 1))
+        for line in b:
+            print("  " + line)
+    sys.exit(0)
+
+sys.path.insert(0, ROOT)
 os.environ["NPGX_SPLIT_DEBUG"] = "1"
 os.environ["NPGX_JOB_STATS"] = "1"
 from npge_amd import _capi, synth  # noqa: E402
