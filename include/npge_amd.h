@@ -300,6 +300,23 @@ int npgx_refine_batch(const char* rows, const int64_t* row_off, const int32_t* j
  *   "ExtendLoop"         Pipe ExtendLoop (lua_lib.lua:677-688) to its fixpoint
  *   "AddingLoopBySize"   AddingLoopBySize (src/algo/TrySmth.cpp:157-178) of all
  *                        blocks into an empty target (SmthUnion, :35-155)
+ *   "Joiner"             Joiner (src/algo/Joiner.cpp:27-262): neighbouring blocks
+ *                        collinear on every fragment (Block::match,
+ *                        Block.cpp:193-230; can_join, Joiner.cpp:45-81) joined,
+ *                        blocks by size descending in the stable order of the
+ *                        set; the between-fragments aligned by align_seqs
+ *                        (AbstractAligner.cpp:104-143) in one batch, the rows
+ *                        row + middle + row written by k_join_rows; a joined
+ *                        block is named "00000000" and stands where its
+ *                        chain's head stood.  NPGX_ERR_ARG (set unchanged) when
+ *                        blocks are held or the facing fragments of a pair to
+ *                        join overlap; NPGX_ERR_RANGE for a joined fragment
+ *                        of 2^30 bases or more
+ *   "OriByMajority"      OriByMajority (src/algo/OriByMajority.cpp:25-61): a
+ *                        block with most letters on ori -1 (tie: its smallest
+ *                        fragment by min_pos, max_pos, sequence name has ori
+ *                        -1) is inverted (Block::inverse, Block.cpp:232-236);
+ *                        names, lengths and block order stay
  *   "FragmentsExtender"  FragmentsExtender (src/algo/FragmentsExtender.cpp:87-119)
  *   "FixEnds"            FixEnds (src/algo/FixEnds.cpp:117-144)
  *   "ExtendLoopFast"     Pipe ExtendLoopFast (src/algo/lua_lib.lua:697-709,

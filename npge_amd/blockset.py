@@ -4,8 +4,15 @@ Mirrors the reference's BlockSet + per-block processors of the block build:
 RemoveNonStem, DummyAligner, MetaAligner, FragmentsExtender, FixEnds,
 OverlaplessUnion, ExtendLoopFast, Filter, MoveGaps, CutGaps,
 SelfOverlapsResolver, the Align / LiteAlign pipes (Align.cpp:17-52), Rest,
+Joiner (Joiner.cpp:27-262), OriByMajority (OriByMajority.cpp:25-61),
 AnchorLoopFast and the DraftPangenome driver (lua_lib.lua:1569-1621).
 Alignment work goes to the HIP aligner in one batch per processor pass.
+
+Joiner plans every chain of collinear neighbouring blocks on the host, aligns
+all between-fragments in one batch and writes the joined rows with one
+k_join_rows launch; a joined block stands where its chain's head stood.  It
+raises NpgxError (NPGX_ERR_ARG) and leaves the set unchanged when the facing
+fragments of a pair it would join overlap.
 """
 import ctypes
 

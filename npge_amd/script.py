@@ -209,6 +209,29 @@ class AddingLoopBySize(_EngineProcessor):
 
 
 @register
+class Joiner(_EngineProcessor):
+    """Joiner (Joiner.cpp:27-262): neighbouring blocks that are collinear on
+    every fragment joined, the between-fragments aligned on the GPU."""
+    name = "Joiner"
+    engine_name = "Joiner"
+
+
+@register
+class OriByMajority(_EngineProcessor):
+    """OriByMajority (OriByMajority.cpp:25-61): a block with most of its
+    letters on ori -1 is inverted.  Blocks keep their names and order."""
+    name = "OriByMajority"
+    engine_name = "OriByMajority"
+
+    def run_impl(self):
+        bs = self.block_set()
+        names = [b.name for b in bs.blocks]
+        super().run_impl()
+        for b, n in zip(bs.blocks, names):
+            b.name = n
+
+
+@register
 class RemoveAlignment(Processor):
     """RemoveAlignment: every fragment loses its row."""
     name = "RemoveAlignment"
