@@ -317,6 +317,24 @@ int npgx_refine_batch(const char* rows, const int64_t* row_off, const int32_t* j
  *                        fragment by min_pos, max_pos, sequence name has ori
  *                        -1) is inverted (Block::inverse, Block.cpp:232-236);
  *                        names, lengths and block order stay
+ *   "ReAlign"            ReAlign (src/algo/ReAlign.cpp:23-78), option
+ *                        --force-realign=0|1: every block of two or more
+ *                        fragments with all its rows (has_alignment,
+ *                        block_hash.cpp:179-186) is aligned again from its
+ *                        fragments' texts (align_block: align_seqs +
+ *                        refine_alignment) and takes the new rows when
+ *                        Block::identity (block_stat.cpp:212-225, k_col_stat)
+ *                        grew and (Filter::is_good_block(new) or not
+ *                        is_good_block(old), Filter.cpp:143-174, with the
+ *                        set's Filter options); the other blocks as
+ *                        "MetaAligner".  A replaced block keeps its fragments,
+ *                        their order, its name and its place.  With
+ *                        --force-realign=1 every block of two or more
+ *                        fragments is aligned again unconditionally.  One
+ *                        batch on the caller's rank (no sharding).
+ *                        NPGX_ERR_ARG (set unchanged) when blocks are held,
+ *                        NPGX_ERR_RANGE (set unchanged) for a fragment of 2^30
+ *                        bases or more
  *   "FragmentsExtender"  FragmentsExtender (src/algo/FragmentsExtender.cpp:87-119)
  *   "FixEnds"            FixEnds (src/algo/FixEnds.cpp:117-144)
  *   "ExtendLoopFast"     Pipe ExtendLoopFast (src/algo/lua_lib.lua:697-709,
@@ -463,6 +481,34 @@ int npgx_blockset_copy(const npgx_blockset* b, int64_t* block_start, int32_t* se
  * Independent of the block order; blocks without rows add nothing.  No
  * reference counterpart (tests/helpers.py restates it in numpy). */
 int npgx_blockset_rows_digest(npgx_blockset* b, uint64_t* digest);
+/* AlignmentStat of an aligned block (make_stat with the six-argument
+ * test_column, src/model/block_stat.cpp:111-154, :188-210), computed on the
+ * device by k_col_stat.  Per column the first non-gap letter is `seen`; ident:
+ * every non-gap letter equals it (N is an ordinary letter: N against N is
+ * ident); gap: some row has '-'; pure_gap: no letter at all.  letters counts
+ * every non-gap character of every row (char_to_size.hpp:24-36: what is not
+ * A T G C counts as N).  identity_x1e4 is block_identity (:212-225) in the
+ * reference's 4-digit Decimal arithmetic (Decimal.hpp:86-125), truncated:
+ *   (10000 * ident_nogap + 5000 * ident_gap)
+ *       / (ident_nogap + ident_gap + noident_nogap + noident_gap),
+ * 0 when the denominator is 0.  A block without rows gets alignment_rows = 0,
+ * total = -1, min_fragment_length and zeros elsewhere: the reference reads
+ * such a block as its left-packed texts; that reading is not provided.
+ * spreading and gc are left to the caller (gc follows from letters). */
+typedef struct {
+    int32_t ident_nogap, ident_gap, noident_nogap, noident_gap, pure_gap, total;
+    int32_t alignment_rows, min_fragment_length;
+    int64_t letters[5];        /* A T G C N */
+    int64_t identity_x1e4;     /* block_identity */
+} npgx_block_stat;
+/* per block in set order; out == NULL: only *n.  NPGX_ERR_ARG when cap is
+ * less than the number of blocks */
+int npgx_blockset_block_stats(npgx_blockset* b, npgx_block_stat* out, int64_t cap, int64_t* n);
+/* outcomes of the last "ReAlign": 0 candidates (blocks of two or more
+ * fragments with all rows; with --force-realign=1 every block of two or more
+ * fragments), 1 replaced, 2 identity grew but Filter refused, 3 identity did
+ * not grow.  NPGX_ERR_STATE before any ReAlign */
+int npgx_blockset_realign_counts(const npgx_blockset* b, int64_t out[4]);
 /* blockset_hash (src/model/block_hash.cpp:112-130) */
 int npgx_blockset_hash(const npgx_blockset* b, uint64_t* hash);
 /* ConSeq (replaces ConSeq::process_block_impl, src/algo/ConSeq.cpp:37-50):

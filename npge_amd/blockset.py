@@ -5,8 +5,16 @@ RemoveNonStem, DummyAligner, MetaAligner, FragmentsExtender, FixEnds,
 OverlaplessUnion, ExtendLoopFast, Filter, MoveGaps, CutGaps,
 SelfOverlapsResolver, the Align / LiteAlign pipes (Align.cpp:17-52), Rest,
 Joiner (Joiner.cpp:27-262), OriByMajority (OriByMajority.cpp:25-61),
-AnchorLoopFast and the DraftPangenome driver (lua_lib.lua:1569-1621).
+ReAlign (ReAlign.cpp:23-78), AnchorLoopFast and the DraftPangenome driver
+(lua_lib.lua:1569-1621).
 Alignment work goes to the HIP aligner in one batch per processor pass.
+
+ReAlign aligns every block that has all its rows again from its fragments'
+texts (one decode launch, one aligner batch, one k_refine launch), takes
+Block::identity of the old and the new rows from one k_col_stat launch and
+keeps the new rows where the identity grew and Filter does not object
+(apply("ReAlign"), apply("ReAlign --force-realign=1"); realign_counts()).
+block_stats() gives the same statistics (AlignmentStat) per block.
 
 Joiner plans every chain of collinear neighbouring blocks on the host, aligns
 all between-fragments in one batch and writes the joined rows with one
@@ -40,6 +48,17 @@ class BbStats(ctypes.Structure):
                 ("ms_loop", ctypes.c_double * 8), ("ms_gpu", ctypes.c_double * 12),
                 ("device_iterations", ctypes.c_int64), ("device_sync_iterations", ctypes.c_int64)]
 
+
+class BlockStat(ctypes.Structure):
+    """npgx_block_stat (include/npge_amd.h)."""
+    _fields_ = [("ident_nogap", ctypes.c_int32), ("ident_gap", ctypes.c_int32),
+                ("noident_nogap", ctypes.c_int32), ("noident_gap", ctypes.c_int32),
+                ("pure_gap", ctypes.c_int32), ("total", ctypes.c_int32),
+                ("alignment_rows", ctypes.c_int32), ("min_fragment_length", ctypes.c_int32),
+                ("letters", ctypes.c_int64 * 5), ("identity_x1e4", ctypes.c_int64)]
+
+
+REALIGN_COUNT_NAMES = ["candidates", "replaced", "filter_refused", "not_better"]
 STAGE_NAMES = ["anchor_finder", "stem_dummy", "move_unchanged", "flank_gather", "align_batch",
                "stitch", "fix_ends", "overlapless_union", "blockset_hash", "filter",
                "align_host_prep", "device_wait", "fix_ends_device", "fix_ends_slice",
@@ -76,6 +95,9 @@ def _bind(L):
     L.npgx_blockset_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.npgx_blockset_hash.argtypes = [vp, P(ctypes.c_uint64)]
     L.npgx_blockset_rows_digest.argtypes = [vp, P(ctypes.c_uint64)]
+    if hasattr(L, "npgx_blockset_block_stats"):  # (NPGX_LIB may name an older build)
+        L.npgx_blockset_block_stats.argtypes = [vp, P(BlockStat), i64, P(i64)]
+        L.npgx_blockset_realign_counts.argtypes = [vp, P(i64 * 4)]
     L.npgx_blockset_conseq.argtypes = [vp, vp, vp, P(i64), P(i64)]
     L.npgx_blockset_deconseq.argtypes = [vp, vp, vp]
     L.npgx_blockset_stats.argtypes = [vp, P(BbStats)]
@@ -250,6 +272,33 @@ class BlockSetEngine:
         h = ctypes.c_uint64()
         _capi.check(_capi.lib().npgx_blockset_rows_digest(self._h, ctypes.byref(h)))
         return h.value
+
+    def block_stats(self):
+        """npgx_blockset_block_stats: AlignmentStat of every block in set order
+        (k_col_stat on the device), a list of dicts -- the five column classes,
+        total, alignment_rows, min_fragment_length, letters (A T G C N) and
+        identity_x1e4 (block_identity, truncated to four digits).  A block
+        without rows has alignment_rows 0 and total -1."""
+        L = _bind(_capi.lib())
+        n = ctypes.c_int64()
+        _capi.check(L.npgx_blockset_block_stats(self._h, None, 0, ctypes.byref(n)))
+        out = (BlockStat * max(n.value, 1))()
+        _capi.check(L.npgx_blockset_block_stats(self._h, out, n.value, ctypes.byref(n)))
+        res = []
+        for s in out[:n.value]:
+            d = {k: int(getattr(s, k)) for k, _ in BlockStat._fields_ if k != "letters"}
+            d["letters"] = [int(x) for x in s.letters]
+            res.append(d)
+        return res
+
+    def realign_counts(self):
+        """Outcomes of the last apply("ReAlign"): candidates, replaced,
+        filter_refused (identity grew, Filter kept the old rows), not_better.
+        NpgxError (NPGX_ERR_STATE) before any ReAlign."""
+        L = _bind(_capi.lib())
+        out = (ctypes.c_int64 * 4)()
+        _capi.check(L.npgx_blockset_realign_counts(self._h, ctypes.byref(out)))
+        return dict(zip(REALIGN_COUNT_NAMES, (int(x) for x in out)))
 
     def stats(self):
         st = BbStats()

@@ -232,6 +232,29 @@ class OriByMajority(_EngineProcessor):
 
 
 @register
+class ReAlign(_EngineProcessor):
+    """ReAlign (ReAlign.cpp:23-78): every aligned block aligned again, the new
+    rows kept where Block::identity grew and Filter does not object; with
+    force-realign every block of two or more fragments takes its new rows.
+    Blocks keep their names and order."""
+    name = "ReAlign"
+
+    def __init__(self):
+        super().__init__()
+        self.add_opt("force-realign", "If realigned block is worse, realign anyway", False)
+
+    def engine_processor(self):
+        return "ReAlign --force-realign=%d" % int(bool(self.opt_value("force-realign")))
+
+    def run_impl(self):
+        bs = self.block_set()
+        names = [b.name for b in bs.blocks]
+        super().run_impl()
+        for b, n in zip(bs.blocks, names):
+            b.name = n
+
+
+@register
 class RemoveAlignment(Processor):
     """RemoveAlignment: every fragment loses its row."""
     name = "RemoveAlignment"
