@@ -335,6 +335,26 @@ int npgx_refine_batch(const char* rows, const int64_t* row_off, const int32_t* j
  *                        NPGX_ERR_ARG (set unchanged) when blocks are held,
  *                        NPGX_ERR_RANGE (set unchanged) for a fragment of 2^30
  *                        bases or more
+ *   "TrySmth"            TrySmth (src/algo/TrySmth.cpp:184-199), option
+ *                        --smth-processor:=NAME; every other option token is
+ *                        NAME's own, parsed as when NAME is applied alone
+ *                        ("TrySmth --smth-processor:=FragmentsExtender
+ *                        --extend-length-portion:=0.5").  The set is copied
+ *                        (clones with rows of their own, named by UniqueNames);
+ *                        NAME runs on the set (af is handed to it); the
+ *                        blocks' names are removed, "ReAlign", "Align"; then
+ *                        AddingLoopBySize over the copy's blocks in their
+ *                        order followed by the new blocks in theirs: by size,
+ *                        alignment length and name, all descending, so the
+ *                        larger version of a block wins and a named original
+ *                        wins a tie against its unnamed equal; what overlaps
+ *                        the winners is cut into pieces (SmthUnion).  Then
+ *                        UniqueNames, "ReAlign", "Align".  NPGX_ERR_ARG (set
+ *                        unchanged) when --smth-processor is missing, NAME is
+ *                        no processor of this list, NAME is "TrySmth" or
+ *                        "DraftPangenome", or blocks are held.  When a step
+ *                        fails the set gets its blocks back as they came
+ *                        (fragments, rows, names) and the error is passed on.
  *   "FragmentsExtender"  FragmentsExtender (src/algo/FragmentsExtender.cpp:87-119)
  *   "FixEnds"            FixEnds (src/algo/FixEnds.cpp:117-144)
  *   "ExtendLoopFast"     Pipe ExtendLoopFast (src/algo/lua_lib.lua:697-709,
@@ -447,6 +467,11 @@ int npgx_blockset_create_sharing(const npgx_seqset* s, const npgx_bb_options* o,
  *   "stage-clock" 1: DraftPangenome records HIP events at its stage
  *                boundaries and fills npgx_bb_stats.ms_gpu (each marker costs
  *                the GPU a few microseconds: diagnostics only); 0: off (default).
+ *   "smth-rows"  how SmthUnion (AddingLoopBySize, ExtendLoop, AnchorLoop,
+ *                TrySmth) reads the rows of the blocks it cuts: 1 (default)
+ *                from their letter maps (k_letter_map: one bit a cell and a
+ *                prefix count a word, about 0.19 B a cell downloaded); 0 from a
+ *                host copy of the rows (1 B a cell), kept for parity tests.
  * NPGX_ERR_ARG for an unknown key or a value out of range. */
 int npgx_blockset_tune(npgx_blockset* b, const char* key, int64_t value);
 /* replace the blocks; row_off == NULL: no rows, else row i = rows[row_off[i]..row_off[i+1])
@@ -509,6 +534,25 @@ int npgx_blockset_block_stats(npgx_blockset* b, npgx_block_stat* out, int64_t ca
  * fragments), 1 replaced, 2 identity grew but Filter refused, 3 identity did
  * not grow.  NPGX_ERR_STATE before any ReAlign */
 int npgx_blockset_realign_counts(const npgx_blockset* b, int64_t out[4]);
+/* the last "TrySmth": 0 blocks in, 1 blocks after the processor + ReAlign +
+ * Align, 2 AddingLoopBySize rounds, 3 blocks SmthUnion cut (split_block), 4
+ * pieces made, 5 blocks out, 6 bytes of letter maps downloaded, 7 bytes of
+ * rows downloaded (0 with "smth-rows" 1).  NPGX_ERR_STATE before any TrySmth */
+int npgx_blockset_try_smth_counts(const npgx_blockset* b, int64_t out[8]);
+/* SmthUnion's running totals over the life of the set: 0 bytes of letter maps
+ * downloaded, 1 bytes of rows downloaded, 2 blocks cut, 3 pieces made */
+int npgx_blockset_smth_counts(const npgx_blockset* b, int64_t out[4]);
+/* the blocks' names in set order, each followed by '\n'; out == NULL: only
+ * *bytes.  NPGX_ERR_ARG when cap is less than *bytes */
+int npgx_blockset_block_names(const npgx_blockset* b, char* out, int64_t cap, int64_t* bytes);
+/* (diagnostic) the letter map of every row of every block with rows, in set
+ * order, as k_letter_map computes it for SmthUnion: a row of L columns has
+ * ceil(L / 64) words, bit c of word w set when column 64 w + c holds a letter
+ * (not '-'; the last word's tail bits are 0), and prefix[w] = the letters of
+ * the row before word w (the kernel's in-tile prefix plus the tile bases the
+ * host adds).  The rows' words follow one another.  words == NULL: only
+ * *n_words.  NPGX_ERR_ARG when cap is less than *n_words */
+int npgx_blockset_letter_map(npgx_blockset* b, uint64_t* words, int64_t* prefix, int64_t cap, int64_t* n_words);
 /* blockset_hash (src/model/block_hash.cpp:112-130) */
 int npgx_blockset_hash(const npgx_blockset* b, uint64_t* hash);
 /* ConSeq (replaces ConSeq::process_block_impl, src/algo/ConSeq.cpp:37-50):

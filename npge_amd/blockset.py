@@ -5,8 +5,8 @@ RemoveNonStem, DummyAligner, MetaAligner, FragmentsExtender, FixEnds,
 OverlaplessUnion, ExtendLoopFast, Filter, MoveGaps, CutGaps,
 SelfOverlapsResolver, the Align / LiteAlign pipes (Align.cpp:17-52), Rest,
 Joiner (Joiner.cpp:27-262), OriByMajority (OriByMajority.cpp:25-61),
-ReAlign (ReAlign.cpp:23-78), AnchorLoopFast and the DraftPangenome driver
-(lua_lib.lua:1569-1621).
+ReAlign (ReAlign.cpp:23-78), TrySmth (TrySmth.cpp:184-199), AnchorLoopFast and
+the DraftPangenome driver (lua_lib.lua:1569-1621).
 Alignment work goes to the HIP aligner in one batch per processor pass.
 
 ReAlign aligns every block that has all its rows again from its fragments'
@@ -21,6 +21,17 @@ all between-fragments in one batch and writes the joined rows with one
 k_join_rows launch; a joined block stands where its chain's head stood.  It
 raises NpgxError (NPGX_ERR_ARG) and leaves the set unchanged when the facing
 fragments of a pair it would join overlap.
+
+TrySmth (apply("TrySmth --smth-processor:=NAME [NAME's options]")) copies the
+set, runs NAME, ReAlign and Align on it, and lets AddingLoopBySize merge the
+copy and the new blocks: the larger version of every block wins, a named
+original wins a tie, what overlaps the winners is cut into pieces.  A failing
+step gives the set back as it came.  try_smth_counts() has the last run's
+counts, block_names() the names UniqueNames gave.  SmthUnion reads the rows of
+the blocks it cuts through their letter maps (k_letter_map: one bit a cell,
+one prefix count a word; tune("smth-rows", 0) for the host copy of the rows);
+letter_map() returns the maps of the set's rows, smth_counts() the bytes both
+paths downloaded.
 """
 import ctypes
 
@@ -58,6 +69,9 @@ class BlockStat(ctypes.Structure):
                 ("letters", ctypes.c_int64 * 5), ("identity_x1e4", ctypes.c_int64)]
 
 
+TRY_SMTH_COUNT_NAMES = ["blocks_in", "blocks_tried", "rounds", "blocks_cut", "pieces", "blocks_out",
+                        "map_bytes", "row_bytes"]
+SMTH_COUNT_NAMES = ["map_bytes", "row_bytes", "blocks_cut", "pieces"]
 REALIGN_COUNT_NAMES = ["candidates", "replaced", "filter_refused", "not_better"]
 STAGE_NAMES = ["anchor_finder", "stem_dummy", "move_unchanged", "flank_gather", "align_batch",
                "stitch", "fix_ends", "overlapless_union", "blockset_hash", "filter",
@@ -98,6 +112,11 @@ def _bind(L):
     if hasattr(L, "npgx_blockset_block_stats"):  # (NPGX_LIB may name an older build)
         L.npgx_blockset_block_stats.argtypes = [vp, P(BlockStat), i64, P(i64)]
         L.npgx_blockset_realign_counts.argtypes = [vp, P(i64 * 4)]
+    if hasattr(L, "npgx_blockset_try_smth_counts"):  # (as above)
+        L.npgx_blockset_try_smth_counts.argtypes = [vp, P(i64 * 8)]
+        L.npgx_blockset_smth_counts.argtypes = [vp, P(i64 * 4)]
+        L.npgx_blockset_block_names.argtypes = [vp, vp, i64, P(i64)]
+        L.npgx_blockset_letter_map.argtypes = [vp, vp, vp, i64, P(i64)]
     L.npgx_blockset_conseq.argtypes = [vp, vp, vp, P(i64), P(i64)]
     L.npgx_blockset_deconseq.argtypes = [vp, vp, vp]
     L.npgx_blockset_stats.argtypes = [vp, P(BbStats)]
@@ -257,7 +276,9 @@ class BlockSetEngine:
         before the prefix search; 0 = never, the low-scratch kernels) or
         "elf-device" (1 / 0 / -1: ExtendLoopFast on the device / host /
         default) or "stage-clock" (1: DraftPangenome fills stats()["ms_gpu"],
-        its GPU timeline by stage).  Results do not change."""
+        its GPU timeline by stage) or "smth-rows" (1: SmthUnion cuts from
+        letter maps, the default; 0: from a host copy of the rows).  Results
+        do not change."""
         _capi.check(_capi.lib().npgx_blockset_tune(self._h, key.encode(), ctypes.c_int64(int(value))))
         return self
 
@@ -299,6 +320,58 @@ class BlockSetEngine:
         out = (ctypes.c_int64 * 4)()
         _capi.check(L.npgx_blockset_realign_counts(self._h, ctypes.byref(out)))
         return dict(zip(REALIGN_COUNT_NAMES, (int(x) for x in out)))
+
+    def try_smth_counts(self):
+        """Counts of the last apply("TrySmth ..."): blocks_in, blocks_tried
+        (after the processor, ReAlign and Align), AddingLoopBySize rounds,
+        blocks_cut, pieces, blocks_out, map_bytes and row_bytes downloaded by
+        SmthUnion.  NpgxError (NPGX_ERR_STATE) before any TrySmth."""
+        L = _bind(_capi.lib())
+        out = (ctypes.c_int64 * 8)()
+        _capi.check(L.npgx_blockset_try_smth_counts(self._h, ctypes.byref(out)))
+        return dict(zip(TRY_SMTH_COUNT_NAMES, (int(x) for x in out)))
+
+    def smth_counts(self):
+        """SmthUnion's running totals on this set: map_bytes and row_bytes
+        downloaded, blocks_cut, pieces."""
+        L = _bind(_capi.lib())
+        out = (ctypes.c_int64 * 4)()
+        _capi.check(L.npgx_blockset_smth_counts(self._h, ctypes.byref(out)))
+        return dict(zip(SMTH_COUNT_NAMES, (int(x) for x in out)))
+
+    def block_names(self):
+        """The blocks' names in set order ("00000000": a new block's)."""
+        L = _bind(_capi.lib())
+        n = ctypes.c_int64()
+        _capi.check(L.npgx_blockset_block_names(self._h, None, 0, ctypes.byref(n)))
+        buf = ctypes.create_string_buffer(max(n.value, 1))
+        _capi.check(L.npgx_blockset_block_names(self._h, ctypes.cast(buf, ctypes.c_void_p), n.value, ctypes.byref(n)))
+        return buf.raw[:n.value].decode().split("\n")[:-1]
+
+    def letter_map(self):
+        """(diagnostic) k_letter_map over every row of every block with rows,
+        in set order: a list of (words, prefix) per row -- uint64 words, bit c
+        of word w set when column 64 w + c holds a letter, and int64 prefix[w]
+        = the row's letters before word w."""
+        L = _bind(_capi.lib())
+        n = ctypes.c_int64()
+        _capi.check(L.npgx_blockset_letter_map(self._h, None, None, 0, ctypes.byref(n)))
+        words = np.zeros(max(n.value, 1), dtype=np.uint64)
+        pre = np.zeros(max(n.value, 1), dtype=np.int64)
+        _capi.check(L.npgx_blockset_letter_map(self._h, _capi.ptr(words), _capi.ptr(pre), n.value, ctypes.byref(n)))
+        nf = len(self.fragments()[1])
+        out, at = [], 0
+        ro = np.zeros(nf + 1, dtype=np.int64)  # the rows' lengths (no row is downloaded)
+        _capi.check(L.npgx_blockset_copy(self._h, None, None, None, None, None, _capi.ptr(ro), None))
+        for i in range(len(ro) - 1):
+            ln = int(ro[i + 1] - ro[i])
+            if ln == 0:
+                continue
+            nw = (ln + 63) // 64
+            out.append((words[at:at + nw].copy(), pre[at:at + nw].copy()))
+            at += nw
+        assert at == n.value
+        return out
 
     def stats(self):
         st = BbStats()

@@ -1580,7 +1580,7 @@ static bool elf_device_mode(const npgx_blockset* B) {
 }
 static bool elf_device_ok(const npgx_blockset* B) {
     if (!elf_device_mode(B)) return false;
-    if (B->comm || !B->held.empty()) return false;
+    if (B->comm || !B->held.empty() || !B->saved.empty()) return false;
     size_t nf = 0;
     for (const Block& b : B->blocks) {
         if (b.name != NULL_BLOCK_NAME) return false;

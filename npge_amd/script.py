@@ -61,6 +61,10 @@ class _EngineProcessor(Processor):
         eng.set_blocks(blocks).apply(self.engine_processor())
         bs.blocks = [Block([Fragment(bs.seqs[q], mn, mx, ori, row) for q, mn, mx, ori, row in blk])
                      for blk in eng.blocks()]
+        self.after_apply(eng, bs)
+
+    def after_apply(self, eng, bs):
+        """What a processor takes from the engine besides the blocks."""
 
 
 @register
@@ -251,6 +255,35 @@ class ReAlign(_EngineProcessor):
         names = [b.name for b in bs.blocks]
         super().run_impl()
         for b, n in zip(bs.blocks, names):
+            b.name = n
+
+
+@register
+class TrySmth(_EngineProcessor):
+    """TrySmth (TrySmth.cpp:184-199): the processor smth-processor (with the
+    options smth-opts, as in its own option string) runs on the set, then
+    ReAlign and Align; AddingLoopBySize merges the set as it was and the new
+    blocks, the larger version of every block winning.
+
+    Limit: the engine gets the fragments and rows, not the blocks' names
+    (npgx_blockset_set_blocks has no names), so a named input block is renamed
+    by UniqueNames where the reference keeps its name, and BlockLengthLess's
+    name term orders ties by those names.  The blocks come back with the names
+    UniqueNames gave them."""
+    name = "TrySmth"
+
+    def __init__(self):
+        super().__init__()
+        self.add_opt("smth-processor", "processor to try", "")
+        self.add_opt("smth-opts", "options of that processor", "")
+        self.add_opt_rule("smth-processor is set", lambda p: bool(p.opt_value("smth-processor")))
+
+    def engine_processor(self):
+        return " ".join(["TrySmth", "--smth-processor:=" + self.opt_value("smth-processor")] +
+                        self.opt_value("smth-opts").split())
+
+    def after_apply(self, eng, bs):
+        for b, n in zip(bs.blocks, eng.block_names()):
             b.name = n
 
 
