@@ -262,6 +262,17 @@ void npgx_aligner_free(npgx_aligner* a);
  * valid (pure-gap columns are removed). */
 int npgx_refine_batch(const char* rows, const int64_t* row_off, const int32_t* job_row_start, int32_t n_jobs,
                       char* out, int32_t* out_len);
+/* The same with the chunked path's knobs (npgx_blockset_tune "refine-chunk" /
+ * "refine-min-len"; -1: the default, 256 / 1024): an alignment of at least
+ * min_len columns is cut where two neighbouring columns both hold one letter
+ * in every row, no gap, and the two letters differ; the pieces are refined
+ * independently (one wave each) and laid end to end, which gives the same
+ * bytes as refining the whole.  The first cut of every tile of `chunk`
+ * columns is used; chunk = 0: no cutting; otherwise a multiple of 64
+ * (NPGX_ERR_ARG).  counts_out (may be NULL): 0 jobs, 1 long jobs, 2 chunks of
+ * the long jobs, 3 longest chunk (columns), 4 columns in, 5 columns out. */
+int npgx_refine_batch_ex(const char* rows, const int64_t* row_off, const int32_t* job_row_start, int32_t n_jobs,
+                         char* out, int32_t* out_len, int32_t chunk, int32_t min_len, int64_t* counts_out);
 
 
 /* ------------------------------------------------------------------ block sets
@@ -355,6 +366,32 @@ int npgx_refine_batch(const char* rows, const int64_t* row_off, const int32_t* j
  *                        "DraftPangenome", or blocks are held.  When a step
  *                        fails the set gets its blocks back as they came
  *                        (fragments, rows, names) and the error is passed on.
+ *   "LiteFilter"         LiteFilter (src/algo/Filter.cpp:29-79), options
+ *                        --min-fragment (default: min_fragment of the options
+ *                        below, MIN_LENGTH) and --min-block (default 2): a
+ *                        block of fewer fragments or a shorter alignment
+ *                        leaves the set; --remove-fragments is accepted and,
+ *                        as in the reference, never read
+ *   "MergeUnique"        MergeUnique (src/algo/MergeUnique.cpp:24-169), options
+ *                        --both-neighbours (default 1) and --merge-long
+ *                        (default 0): unique fragments (blocks of one
+ *                        fragment shorter than min_fragment) that stand next
+ *                        to the fragments of one block, on the same side, and
+ *                        with --both-neighbours=1 have their other neighbour
+ *                        in one block at one relative ori, become a block
+ *                        named "m<size>x<alignment length>", appended to the
+ *                        set; each takes the ori of its neighbour.  The new
+ *                        block has rows when all its fragments had rows of
+ *                        one length (a flipped fragment's gapless row is
+ *                        reverse-complemented; a gapped one: NPGX_ERR_ARG,
+ *                        set unchanged), else none.  NPGX_ERR_ARG (set
+ *                        unchanged) when blocks are held.  Host work.
+ *   "JoinerP"            LiteFilter, OriByMajority, Rest, MergeUnique,
+ *                        MetaAligner, Joiner, Rest (lua_lib.lua:641-651)
+ *   "MergeAndJoin"       Rest, MergeUnique, MetaAligner, Joiner (:653-660)
+ *   "LiteJoinerP"        LiteFilter, OriByMajority, Joiner (:662-668); the
+ *                        three pipes take no options, and a step's refusal
+ *                        is passed on
  *   "FragmentsExtender"  FragmentsExtender (src/algo/FragmentsExtender.cpp:87-119)
  *   "FixEnds"            FixEnds (src/algo/FixEnds.cpp:117-144)
  *   "ExtendLoopFast"     Pipe ExtendLoopFast (src/algo/lua_lib.lua:697-709,
@@ -472,6 +509,12 @@ int npgx_blockset_create_sharing(const npgx_seqset* s, const npgx_bb_options* o,
  *                from their letter maps (k_letter_map: one bit a cell and a
  *                prefix count a word, about 0.19 B a cell downloaded); 0 from a
  *                host copy of the rows (1 B a cell), kept for parity tests.
+ *   "refine-chunk" refine_alignment of a long block in independent chunks
+ *                (npgx_refine_batch_ex): the tile, in columns, of which the
+ *                first cut is used (default 256; a multiple of 64); 0: every
+ *                block is refined by one wave.
+ *   "refine-min-len" blocks of at least this many columns take the chunked
+ *                path (default 1024; >= 0).
  * NPGX_ERR_ARG for an unknown key or a value out of range. */
 int npgx_blockset_tune(npgx_blockset* b, const char* key, int64_t value);
 /* replace the blocks; row_off == NULL: no rows, else row i = rows[row_off[i]..row_off[i+1])
@@ -539,6 +582,15 @@ int npgx_blockset_realign_counts(const npgx_blockset* b, int64_t out[4]);
  * pieces made, 5 blocks out, 6 bytes of letter maps downloaded, 7 bytes of
  * rows downloaded (0 with "smth-rows" 1).  NPGX_ERR_STATE before any TrySmth */
 int npgx_blockset_try_smth_counts(const npgx_blockset* b, int64_t out[8]);
+/* refine_alignment over the last apply (every k_refine batch of it): 0 jobs,
+ * 1 long jobs (at least "refine-min-len" columns, cut into chunks), 2 their
+ * chunks, 3 the longest chunk (columns), 4 columns in, 5 columns out (layout
+ * of npgx_refine_batch_ex's counts_out) */
+int npgx_blockset_refine_counts(const npgx_blockset* b, int64_t out[6]);
+/* the last "MergeUnique" (alone or inside "JoinerP" / "MergeAndJoin"): 0
+ * blocks inspected (two or more fragments), 1 merges (new blocks), 2
+ * fragments merged.  NPGX_ERR_STATE before any MergeUnique */
+int npgx_blockset_merge_unique_counts(const npgx_blockset* b, int64_t out[3]);
 /* SmthUnion's running totals over the life of the set: 0 bytes of letter maps
  * downloaded, 1 bytes of rows downloaded, 2 blocks cut, 3 pieces made */
 int npgx_blockset_smth_counts(const npgx_blockset* b, int64_t out[4]);

@@ -15,14 +15,26 @@ from .processor import Decimal, Processor, register
 ALIGNER_TYPES = {"similar": 0, "dummy": 1}
 
 
-def refine_batch(alignments):
+REFINE_COUNT_NAMES = ["jobs", "long_jobs", "chunks", "longest_chunk", "columns_in", "columns_out"]
+
+
+def refine_batch(alignments, chunk=None, min_len=None, counts=None):
     """refine_alignment (refine_alignment.cpp:182-190) of each alignment (a
-    list of equal-length gapped rows) on the GPU (npgx_refine_batch)."""
+    list of equal-length gapped rows) on the GPU (npgx_refine_batch_ex).
+    chunk / min_len: an alignment of at least min_len columns is refined in
+    independent chunks, cut at the first cut of every tile of `chunk` columns
+    (a multiple of 64; 0: never; None: the library's defaults); the result
+    does not depend on them.  counts: a dict that receives
+    REFINE_COUNT_NAMES."""
     L = _capi.lib()
     if not getattr(L, "_refine_bound", False):
         vp = ctypes.c_void_p
         L.npgx_refine_batch.argtypes = [vp, vp, vp, ctypes.c_int32, vp, vp]
+        L.npgx_refine_batch_ex.argtypes = [vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32, vp]
         L._refine_bound = True
+    for v in (chunk, min_len):
+        if v is not None and not 0 <= int(v) < 2 ** 31:
+            raise ValueError("chunk and min_len are None or in [0, 2^31)")
     rows = [r for a in alignments for r in a]
     data = "".join(rows).encode()
     off = np.zeros(len(rows) + 1, dtype=np.int64)
@@ -32,8 +44,13 @@ def refine_batch(alignments):
     buf = ctypes.create_string_buffer(data, max(len(data), 1))
     out = ctypes.create_string_buffer(max(len(data), 1))
     lens = np.zeros(max(len(alignments), 1), dtype=np.int32)
-    _capi.check(L.npgx_refine_batch(ctypes.cast(buf, ctypes.c_void_p), _capi.ptr(off), _capi.ptr(jstart),
-                                    len(alignments), ctypes.cast(out, ctypes.c_void_p), _capi.ptr(lens)))
+    cnt = np.zeros(len(REFINE_COUNT_NAMES), dtype=np.int64)
+    _capi.check(L.npgx_refine_batch_ex(ctypes.cast(buf, ctypes.c_void_p), _capi.ptr(off), _capi.ptr(jstart),
+                                       len(alignments), ctypes.cast(out, ctypes.c_void_p), _capi.ptr(lens),
+                                       -1 if chunk is None else int(chunk), -1 if min_len is None else int(min_len),
+                                       _capi.ptr(cnt)))
+    if counts is not None:
+        counts.update(zip(REFINE_COUNT_NAMES, (int(x) for x in cnt)))
     raw = out.raw
     res, k = [], 0
     for j, a in enumerate(alignments):

@@ -32,6 +32,18 @@ the blocks it cuts through their letter maps (k_letter_map: one bit a cell,
 one prefix count a word; tune("smth-rows", 0) for the host copy of the rows);
 letter_map() returns the maps of the set's rows, smth_counts() the bytes both
 paths downloaded.
+
+LiteFilter (apply("LiteFilter --min-fragment=N --min-block=K")) drops small
+blocks; MergeUnique (apply("MergeUnique --both-neighbours=0 --merge-long=1"),
+merge_unique_counts()) merges unique fragments with common neighbours into
+blocks named "m<size>x<length>"; JoinerP, MergeAndJoin and LiteJoinerP are the
+reference's pipes over them, Rest, OriByMajority, MetaAligner and Joiner
+(lua_lib.lua:641-668), each one apply and each accepted by TrySmth.
+
+refine_alignment takes a block of at least "refine-min-len" columns in
+independent chunks (tune("refine-chunk", N); k_refine_cuts finds the cuts, the
+chunks are k_refine jobs, k_join_rows gathers them), bit-identical to one wave
+per block; refine_counts() has the last apply's jobs, long jobs and chunks.
 """
 import ctypes
 
@@ -72,6 +84,8 @@ class BlockStat(ctypes.Structure):
 TRY_SMTH_COUNT_NAMES = ["blocks_in", "blocks_tried", "rounds", "blocks_cut", "pieces", "blocks_out",
                         "map_bytes", "row_bytes"]
 SMTH_COUNT_NAMES = ["map_bytes", "row_bytes", "blocks_cut", "pieces"]
+MERGE_UNIQUE_COUNT_NAMES = ["blocks_inspected", "merges", "fragments_merged"]
+REFINE_COUNT_NAMES = ["jobs", "long_jobs", "chunks", "longest_chunk", "columns_in", "columns_out"]
 REALIGN_COUNT_NAMES = ["candidates", "replaced", "filter_refused", "not_better"]
 STAGE_NAMES = ["anchor_finder", "stem_dummy", "move_unchanged", "flank_gather", "align_batch",
                "stitch", "fix_ends", "overlapless_union", "blockset_hash", "filter",
@@ -117,6 +131,9 @@ def _bind(L):
         L.npgx_blockset_smth_counts.argtypes = [vp, P(i64 * 4)]
         L.npgx_blockset_block_names.argtypes = [vp, vp, i64, P(i64)]
         L.npgx_blockset_letter_map.argtypes = [vp, vp, vp, i64, P(i64)]
+    if hasattr(L, "npgx_blockset_refine_counts"):  # (as above)
+        L.npgx_blockset_refine_counts.argtypes = [vp, P(i64 * 6)]
+        L.npgx_blockset_merge_unique_counts.argtypes = [vp, P(i64 * 3)]
     L.npgx_blockset_conseq.argtypes = [vp, vp, vp, P(i64), P(i64)]
     L.npgx_blockset_deconseq.argtypes = [vp, vp, vp]
     L.npgx_blockset_stats.argtypes = [vp, P(BbStats)]
@@ -277,8 +294,11 @@ class BlockSetEngine:
         "elf-device" (1 / 0 / -1: ExtendLoopFast on the device / host /
         default) or "stage-clock" (1: DraftPangenome fills stats()["ms_gpu"],
         its GPU timeline by stage) or "smth-rows" (1: SmthUnion cuts from
-        letter maps, the default; 0: from a host copy of the rows).  Results
-        do not change."""
+        letter maps, the default; 0: from a host copy of the rows) or
+        "refine-chunk" / "refine-min-len" (blocks of at least refine-min-len
+        columns are refined in independent chunks cut at the first cut of
+        every refine-chunk columns, a multiple of 64; 0: never).  Results do
+        not change."""
         _capi.check(_capi.lib().npgx_blockset_tune(self._h, key.encode(), ctypes.c_int64(int(value))))
         return self
 
@@ -330,6 +350,24 @@ class BlockSetEngine:
         out = (ctypes.c_int64 * 8)()
         _capi.check(L.npgx_blockset_try_smth_counts(self._h, ctypes.byref(out)))
         return dict(zip(TRY_SMTH_COUNT_NAMES, (int(x) for x in out)))
+
+    def merge_unique_counts(self):
+        """The last MergeUnique (alone or inside JoinerP / MergeAndJoin):
+        blocks_inspected, merges, fragments_merged.  NpgxError
+        (NPGX_ERR_STATE) before any MergeUnique."""
+        L = _bind(_capi.lib())
+        out = (ctypes.c_int64 * 3)()
+        _capi.check(L.npgx_blockset_merge_unique_counts(self._h, ctypes.byref(out)))
+        return dict(zip(MERGE_UNIQUE_COUNT_NAMES, (int(x) for x in out)))
+
+    def refine_counts(self):
+        """refine_alignment over the last apply: jobs, long_jobs (at least
+        "refine-min-len" columns: refined in chunks), chunks, longest_chunk,
+        columns_in, columns_out."""
+        L = _bind(_capi.lib())
+        out = (ctypes.c_int64 * 6)()
+        _capi.check(L.npgx_blockset_refine_counts(self._h, ctypes.byref(out)))
+        return dict(zip(REFINE_COUNT_NAMES, (int(x) for x in out)))
 
     def smth_counts(self):
         """SmthUnion's running totals on this set: map_bytes and row_bytes

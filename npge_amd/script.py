@@ -259,6 +259,81 @@ class ReAlign(_EngineProcessor):
 
 
 @register
+class LiteFilter(_EngineProcessor):
+    """LiteFilter (Filter.cpp:29-79): blocks of fewer than min-block fragments
+    or an alignment shorter than min-fragment leave the set.  The others keep
+    their names and order."""
+    name = "LiteFilter"
+
+    def __init__(self):
+        super().__init__()
+        self.add_gopt("min-fragment", "Minimum fragment length", "MIN_LENGTH")
+        self.add_opt("min-block", "Minimum block size", 2)
+        self.add_opt("remove-fragments", "Delete individual fragments instead of whole block (never read)", True)
+
+    def engine_processor(self):
+        return "LiteFilter --min-fragment=%d --min-block=%d" % (self.opt_value("min-fragment"),
+                                                                self.opt_value("min-block"))
+
+    def run_impl(self):
+        bs = self.block_set()
+        names = {tuple((id(f.seq), f.min_pos, f.max_pos, f.ori) for f in b.fragments): b.name for b in bs.blocks}
+        super().run_impl()
+        for b in bs.blocks:
+            b.name = names.get(tuple((id(f.seq), f.min_pos, f.max_pos, f.ori) for f in b.fragments), b.name)
+
+
+class _NamingProcessor(_EngineProcessor):
+    """The blocks come back under the engine's names (new blocks "m<size>x<length>")."""
+
+    def after_apply(self, eng, bs):
+        for b, n in zip(bs.blocks, eng.block_names()):
+            b.name = n
+
+
+@register
+class MergeUnique(_NamingProcessor):
+    """MergeUnique (MergeUnique.cpp:24-169): unique fragments with common
+    neighbours merged into blocks named "m<size>x<length>".
+
+    Limit (as TrySmth's): the engine gets no block names, so the blocks that
+    stay come back named "00000000"."""
+    name = "MergeUnique"
+
+    def __init__(self):
+        super().__init__()
+        self.add_opt("both-neighbours", "Require both neighbours of an unique fragment to be from common blocks",
+                     True)
+        self.add_opt("merge-long", "Merge long fragments (>= MIN_LENGTH) as well", False)
+
+    def engine_processor(self):
+        return "MergeUnique --both-neighbours=%d --merge-long=%d" % (int(bool(self.opt_value("both-neighbours"))),
+                                                                     int(bool(self.opt_value("merge-long"))))
+
+
+@register
+class JoinerP(_NamingProcessor):
+    """JoinerP (lua_lib.lua:641-651): LiteFilter, OriByMajority, Rest,
+    MergeUnique, MetaAligner, Joiner, Rest."""
+    name = "JoinerP"
+    engine_name = "JoinerP"
+
+
+@register
+class MergeAndJoin(_NamingProcessor):
+    """MergeAndJoin (lua_lib.lua:653-660): Rest, MergeUnique, MetaAligner, Joiner."""
+    name = "MergeAndJoin"
+    engine_name = "MergeAndJoin"
+
+
+@register
+class LiteJoinerP(_NamingProcessor):
+    """LiteJoinerP (lua_lib.lua:662-668): LiteFilter, OriByMajority, Joiner."""
+    name = "LiteJoinerP"
+    engine_name = "LiteJoinerP"
+
+
+@register
 class TrySmth(_EngineProcessor):
     """TrySmth (TrySmth.cpp:184-199): the processor smth-processor (with the
     options smth-opts, as in its own option string) runs on the set, then
