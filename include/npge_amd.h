@@ -363,7 +363,9 @@ int npgx_refine_batch_ex(const char* rows, const int64_t* row_off, const int32_t
  *                        UniqueNames, "ReAlign", "Align".  NPGX_ERR_ARG (set
  *                        unchanged) when --smth-processor is missing, NAME is
  *                        no processor of this list, NAME is "TrySmth" or
- *                        "DraftPangenome", or blocks are held.  When a step
+ *                        "DraftPangenome", NAME is "GlobalTree", "PrintTree"
+ *                        or "FragmentDistance" (they change no block), or
+ *                        blocks are held.  When a step
  *                        fails the set gets its blocks back as they came
  *                        (fragments, rows, names) and the error is passed on.
  *   "LiteFilter"         LiteFilter (src/algo/Filter.cpp:29-79), options
@@ -398,7 +400,26 @@ int npgx_refine_batch_ex(const char* rows, const int64_t* row_off, const int32_t
  *                        src/algo/Pipe.cpp:60-78)
  *   "Filter"             Filter (src/algo/Filter.cpp:208-248)
  *   "DraftPangenome"     AnchorFinder -> RemoveNonStem -> DummyAligner ->
- *                        ExtendLoopFast -> Filter (lua_lib.lua:1569-1621) */
+ *                        ExtendLoopFast -> Filter (lua_lib.lua:1569-1621)
+ *   "FragmentDistance"   FragmentDistance (src/algo/FragmentDistance.cpp:31-69):
+ *                        the penalty of every pair of rows of every block
+ *                        (k_pair_dist), kept for npgx_blockset_pair_distances;
+ *                        --distance-file is accepted (the engine writes no
+ *                        file)
+ *   "PrintTree"          PrintTree (src/algo/PrintTree.cpp:51-67), option
+ *                        --tree-method nj (default) | upgma (--tree-file is
+ *                        accepted): a tree of every block, kept for
+ *                        npgx_blockset_block_trees
+ *   "GlobalTree"         GlobalTree (src/algo/GlobalTree.cpp:85-116), options
+ *                        --bootstrap-print no | in-braces | before-length
+ *                        (default) and --tree-pseudo-leafs (--out-global-tree
+ *                        is accepted): the tree of the genomes, kept for
+ *                        npgx_blockset_global_tree.  These three change no
+ *                        block; an unknown option or value is NPGX_ERR_ARG.
+ *
+ * Known limits: GlobalTree takes at most 64 genomes (k_clade_diag's row masks
+ * are 64 bits; NPGX_ERR_RANGE before anything is launched); fragment
+ * distances and block trees have no row limit. */
 typedef struct npgx_blockset npgx_blockset;
 
 typedef struct {
@@ -572,6 +593,71 @@ typedef struct {
 /* per block in set order; out == NULL: only *n.  NPGX_ERR_ARG when cap is
  * less than the number of blocks */
 int npgx_blockset_block_stats(npgx_blockset* b, npgx_block_stat* out, int64_t cap, int64_t* n);
+/* ---- trees and fragment distances.  None of these calls changes the set.
+ * Each follows the two-call size protocol: a call without output buffers
+ * computes, keeps the result and gives the sizes; a call with them copies the
+ * kept result out (computing it first when none is kept).  npgx_blockset_apply
+ * and the calls that replace or add blocks drop what is kept; apply's
+ * "FragmentDistance", "PrintTree" and "GlobalTree" keep theirs for these calls.
+ *
+ * FragmentDistance::fragment_distance (src/algo/FragmentDistance.cpp:31-69) of
+ * every pair of rows of every block, blocks in set order: block k's pairs are
+ * penalty[pair_start[k] .. pair_start[k + 1]) in (i ascending, j ascending)
+ * order, i < j its fragments in block order; the penalty counts the columns c
+ * in [1, L - 2] that differ while columns c - 1 and c + 1 are equal and no gap
+ * ('-' against '-' is equal, a letter against '-' is not).  Distance.total is
+ * the block's length (npgx_blockset_copy).  A block of one fragment has no
+ * pairs; NPGX_ERR_STATE when a block of two or more fragments has no rows
+ * ("Fragment without alignment").  pair_start holds *n_blocks + 1 entries;
+ * NPGX_ERR_ARG when cap is less than *n_pairs. */
+int npgx_blockset_pair_distances(npgx_blockset* b, int64_t* pair_start, int32_t* penalty, int64_t cap,
+                                 int64_t* n_blocks, int64_t* n_pairs);
+/* GlobalTree's add_dist (src/algo/GlobalTree.cpp:68-83) over the blocks that
+ * "RemoveNonStem --exact" would keep (the set is neither cloned nor filtered):
+ * out[g1 * G + g2] = the penalties summed over the stem blocks' pairs of the
+ * genomes g1 and g2, genomes in genomes_list order (sorted by name,
+ * src/model/block_stat.cpp:255-263).  The sums are made on the device; G * G
+ * integers come back.  n_stem_blocks may be NULL.  NPGX_ERR_ARG when a
+ * sequence names no genome or cap is less than G * G, NPGX_ERR_STATE when a
+ * stem block of two or more fragments has no rows. */
+int npgx_blockset_genome_distances(npgx_blockset* b, int64_t* out, int64_t cap, int32_t* n_genomes,
+                                   int64_t* n_stem_blocks);
+/* one node of a tree in print order: the root first (parent -1), then
+ * all_descendants (src/util/tree.cpp:93-98), parents before children */
+typedef struct {
+    int32_t parent;    /* entry of the parent node */
+    int32_t leaf;      /* a leaf: its genome (global tree) or fragment (block tree);
+                        * -2 - that index: its pseudo leaf ".name"; -1: an internal node */
+    double length;
+    double bootstrap;
+} npgx_tree_node;
+/* GlobalTree::run_impl (src/algo/GlobalTree.cpp:85-116): the genome matrix
+ * above, TreeNode::neighbor_joining, add_diagnostic with min_block = G over the
+ * same stem blocks (a node's bootstrap = the diagnostic columns of its clade,
+ * src/model/block_stat.cpp:236-253, counted by k_clade_diag), optionally
+ * clone_with_pseudo_leafs, newick(true, sbs) and "\n".  options: "" or
+ * "--bootstrap-print=no|in-braces|before-length" (default before-length) and
+ * "--tree-pseudo-leafs=0|1"; anything else is NPGX_ERR_ARG.  Node pairs are
+ * ordered by node number where the reference orders them by address (DESIGN.md
+ * "Determinism conventions").  NPGX_ERR_RANGE for more than 64 genomes, before
+ * anything is launched.  A fetching call copies the kept tree whatever its
+ * options say. */
+int npgx_blockset_global_tree(npgx_blockset* b, const char* options, char* text, int64_t text_cap,
+                              int64_t* text_bytes, npgx_tree_node* nodes, int64_t node_cap, int64_t* n_nodes);
+/* PrintTree::make_tree (src/algo/PrintTree.cpp:51-67) of every block in set
+ * order, method "nj" or "upgma" (else NPGX_ERR_ARG): the leaves are the
+ * block's fragments named by Fragment::id, the distance of two is
+ * double(penalty) / double(total).  Block k's newick text (print_newick with
+ * its defaults: lengths, no bootstrap) is text[text_start[k] ..
+ * text_start[k + 1]), its node table nodes[node_start[k] .. node_start[k + 1])
+ * (both arrays hold *n_blocks + 1 entries and may be NULL).  Neighbour joining
+ * costs the reference's O(n^4) per block of n fragments on the host. */
+int npgx_blockset_block_trees(npgx_blockset* b, const char* method, char* text, int64_t text_cap,
+                              int64_t* text_bytes, int64_t* text_start, int64_t* node_start, npgx_tree_node* nodes,
+                              int64_t node_cap, int64_t* n_blocks, int64_t* n_nodes);
+/* the columns of one k_pair_dist tile for a block of `rows` rows (the tile's
+ * rows are staged in LDS; tests place mismatches at its edges) */
+int32_t npgx_pair_dist_tile_columns(int64_t rows);
 /* outcomes of the last "ReAlign": 0 candidates (blocks of two or more
  * fragments with all rows; with --force-realign=1 every block of two or more
  * fragments), 1 replaced, 2 identity grew but Filter refused, 3 identity did

@@ -166,6 +166,7 @@ class SeqSet:
                                    ctypes.cast(nm, ctypes.c_void_p), n, ctypes.byref(h)))
         self._h = h
         self.n = n
+        self.names = list(names)
         self._keep = None
 
     @property

@@ -40,6 +40,14 @@ blocks named "m<size>x<length>"; JoinerP, MergeAndJoin and LiteJoinerP are the
 reference's pipes over them, Rest, OriByMajority, MetaAligner and Joiner
 (lua_lib.lua:641-668), each one apply and each accepted by TrySmth.
 
+Trees and fragment distances change no block: pair_distances()
+(FragmentDistance, k_pair_dist), genome_distances() (GlobalTree's add_dist over
+the stem blocks, summed on the device), global_tree() (neighbour joining on
+the host, the bootstraps from k_clade_diag's diagnostic columns) and
+block_trees() (PrintTree); apply("FragmentDistance"), apply("PrintTree
+--tree-method=upgma") and apply("GlobalTree --bootstrap-print=no") keep their
+result for those calls and are refused inside TrySmth.
+
 refine_alignment takes a block of at least "refine-min-len" columns in
 independent chunks (tune("refine-chunk", N); k_refine_cuts finds the cuts, the
 chunks are k_refine jobs, k_join_rows gathers them), bit-identical to one wave
@@ -79,6 +87,12 @@ class BlockStat(ctypes.Structure):
                 ("pure_gap", ctypes.c_int32), ("total", ctypes.c_int32),
                 ("alignment_rows", ctypes.c_int32), ("min_fragment_length", ctypes.c_int32),
                 ("letters", ctypes.c_int64 * 5), ("identity_x1e4", ctypes.c_int64)]
+
+
+class TreeNode(ctypes.Structure):
+    """npgx_tree_node (include/npge_amd.h)."""
+    _fields_ = [("parent", ctypes.c_int32), ("leaf", ctypes.c_int32), ("length", ctypes.c_double),
+                ("bootstrap", ctypes.c_double)]
 
 
 TRY_SMTH_COUNT_NAMES = ["blocks_in", "blocks_tried", "rounds", "blocks_cut", "pieces", "blocks_out",
@@ -134,6 +148,14 @@ def _bind(L):
     if hasattr(L, "npgx_blockset_refine_counts"):  # (as above)
         L.npgx_blockset_refine_counts.argtypes = [vp, P(i64 * 6)]
         L.npgx_blockset_merge_unique_counts.argtypes = [vp, P(i64 * 3)]
+    if hasattr(L, "npgx_blockset_pair_distances"):  # (as above)
+        L.npgx_blockset_pair_distances.argtypes = [vp, vp, vp, i64, P(i64), P(i64)]
+        L.npgx_blockset_genome_distances.argtypes = [vp, vp, i64, P(ctypes.c_int32), P(i64)]
+        L.npgx_blockset_global_tree.argtypes = [vp, ctypes.c_char_p, vp, i64, P(i64), P(TreeNode), i64, P(i64)]
+        L.npgx_blockset_block_trees.argtypes = [vp, ctypes.c_char_p, vp, i64, P(i64), vp, vp, P(TreeNode), i64,
+                                                P(i64), P(i64)]
+        L.npgx_pair_dist_tile_columns.argtypes = [i64]
+        L.npgx_pair_dist_tile_columns.restype = ctypes.c_int32
     L.npgx_blockset_conseq.argtypes = [vp, vp, vp, P(i64), P(i64)]
     L.npgx_blockset_deconseq.argtypes = [vp, vp, vp]
     L.npgx_blockset_stats.argtypes = [vp, P(BbStats)]
@@ -149,6 +171,11 @@ def _bind(L):
 
 ALIGN_KEYS = ("mismatch_check", "gap_check", "aligned_check", "align_min_length",
               "align_min_identity_x1e4")
+
+
+def pair_dist_tile_columns(rows):
+    """The columns of one k_pair_dist tile for a block of `rows` rows."""
+    return int(_bind(_capi.lib()).npgx_pair_dist_tile_columns(int(rows)))
 
 
 def default_options(**kw):
@@ -331,6 +358,86 @@ class BlockSetEngine:
             d["letters"] = [int(x) for x in s.letters]
             res.append(d)
         return res
+
+    def pair_distances(self):
+        """npgx_blockset_pair_distances: FragmentDistance::fragment_distance
+        (FragmentDistance.cpp:31-69) of every pair of rows of every block
+        (k_pair_dist), a list per block in set order of the penalties of its
+        pairs (i ascending, j ascending); Distance.total is the block's
+        length.  A block of one fragment has no pairs; NpgxError
+        (NPGX_ERR_STATE) when a block of two or more fragments has no rows."""
+        L = _bind(_capi.lib())
+        nb, npairs = ctypes.c_int64(), ctypes.c_int64()
+        _capi.check(L.npgx_blockset_pair_distances(self._h, None, None, 0, ctypes.byref(nb), ctypes.byref(npairs)))
+        start = np.zeros(nb.value + 1, dtype=np.int64)
+        pen = np.zeros(max(npairs.value, 1), dtype=np.int32)
+        _capi.check(L.npgx_blockset_pair_distances(self._h, _capi.ptr(start), _capi.ptr(pen), npairs.value,
+                                                   ctypes.byref(nb), ctypes.byref(npairs)))
+        return [pen[start[k]:start[k + 1]].tolist() for k in range(nb.value)]
+
+    def genomes(self):
+        """genomes_list (block_stat.cpp:255-263): the sequences' genomes
+        (Sequence::genome), sorted, each once."""
+        from .model import Sequence
+        return sorted({Sequence(n, "").genome() for n in self.ss.names})
+
+    def genome_distances(self):
+        """npgx_blockset_genome_distances: GlobalTree's add_dist
+        (GlobalTree.cpp:68-83) over the blocks RemoveNonStem --exact would
+        keep, summed on the device: the G x G matrix (lists of int) of
+        mutations between the genomes in genomes() order."""
+        L = _bind(_capi.lib())
+        g, ns = ctypes.c_int32(), ctypes.c_int64()
+        _capi.check(L.npgx_blockset_genome_distances(self._h, None, 0, ctypes.byref(g), ctypes.byref(ns)))
+        out = np.zeros(max(g.value * g.value, 1), dtype=np.int64)
+        _capi.check(L.npgx_blockset_genome_distances(self._h, _capi.ptr(out), g.value * g.value, ctypes.byref(g),
+                                                     ctypes.byref(ns)))
+        return out[:g.value * g.value].reshape(g.value, g.value).tolist()
+
+    @staticmethod
+    def _table(nodes, a, b):
+        return [(int(x.parent), int(x.leaf), float(x.length), float(x.bootstrap)) for x in nodes[a:b]]
+
+    def global_tree(self, bootstrap_print="before-length", pseudo_leafs=False):
+        """npgx_blockset_global_tree: GlobalTree::run_impl (GlobalTree.cpp:85-116)
+        -- the genome matrix, TreeNode::neighbor_joining (tree.cpp:360-480),
+        add_diagnostic (ConsensusTree.cpp:294-367; k_clade_diag), optionally
+        clone_with_pseudo_leafs, newick.  Returns (text, nodes): the file's
+        text and the node table in print order, (parent entry, leaf, length,
+        bootstrap) with the root first; leaf = the genome's index in genomes(),
+        -2 - index for its pseudo leaf, -1 for an internal node.  NpgxError
+        (NPGX_ERR_RANGE) for more than 64 genomes, (NPGX_ERR_ARG) for another
+        bootstrap_print than no / in-braces / before-length."""
+        L = _bind(_capi.lib())
+        opts = ("--bootstrap-print=%s --tree-pseudo-leafs=%d" % (bootstrap_print, int(bool(pseudo_leafs)))).encode()
+        tb, nn = ctypes.c_int64(), ctypes.c_int64()
+        _capi.check(L.npgx_blockset_global_tree(self._h, opts, None, 0, ctypes.byref(tb), None, 0, ctypes.byref(nn)))
+        text = ctypes.create_string_buffer(max(tb.value, 1))
+        nodes = (TreeNode * max(nn.value, 1))()
+        _capi.check(L.npgx_blockset_global_tree(self._h, opts, ctypes.cast(text, ctypes.c_void_p), tb.value,
+                                                ctypes.byref(tb), nodes, nn.value, ctypes.byref(nn)))
+        return text.raw[:tb.value].decode(), self._table(nodes, 0, nn.value)
+
+    def block_trees(self, method="nj"):
+        """npgx_blockset_block_trees: PrintTree::make_tree (PrintTree.cpp:51-67)
+        of every block in set order, method "nj" or "upgma" (NpgxError
+        NPGX_ERR_ARG otherwise): a list of (newick, nodes) -- print_newick's
+        text with its defaults and the node table as global_tree's, leaf = the
+        fragment's index in its block (named by Fragment::id in the text)."""
+        L = _bind(_capi.lib())
+        tb, nb, nn = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _capi.check(L.npgx_blockset_block_trees(self._h, method.encode(), None, 0, ctypes.byref(tb), None, None, None,
+                                                0, ctypes.byref(nb), ctypes.byref(nn)))
+        text = ctypes.create_string_buffer(max(tb.value, 1))
+        nodes = (TreeNode * max(nn.value, 1))()
+        ts = np.zeros(nb.value + 1, dtype=np.int64)
+        ns = np.zeros(nb.value + 1, dtype=np.int64)
+        _capi.check(L.npgx_blockset_block_trees(self._h, method.encode(), ctypes.cast(text, ctypes.c_void_p), tb.value,
+                                                ctypes.byref(tb), _capi.ptr(ts), _capi.ptr(ns), nodes, nn.value,
+                                                ctypes.byref(nb), ctypes.byref(nn)))
+        raw = text.raw
+        return [(raw[ts[k]:ts[k + 1]].decode(), self._table(nodes, int(ns[k]), int(ns[k + 1])))
+                for k in range(nb.value)]
 
     def realign_counts(self):
         """Outcomes of the last apply("ReAlign"): candidates, replaced,

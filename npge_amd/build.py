@@ -14,8 +14,11 @@ LIB = os.path.join(HERE, "libnpge_amd.so")
 # (loaded by _capi when NPGX_PROFILE=1)
 LIB_PROF = os.path.join(HERE, "libnpge_amd_prof.so")
 SOURCES = ["seqset.hip", "anchor_finder.hip", "similar_aligner.hip", "block_build.hip",
-           "general_aligner.hip", "wide_aligner.hip", "comm_rccl.hip", "host_sampler.cpp"]
-HEADERS = ["common.hpp", "sa_device.hpp", "log_score.inc", "elf_device.inc"]
+           "general_aligner.hip", "wide_aligner.hip", "comm_rccl.hip", "host_sampler.cpp", "tree.cpp"]
+HEADERS = ["common.hpp", "sa_device.hpp", "log_score.inc", "elf_device.inc", "tree.hpp"]
+# host-only sources with flags of their own: tree.cpp restates the reference's
+# double arithmetic operation by operation, so no multiply-add may be fused
+HOST_FLAGS = {"tree.cpp": ["-ffp-contract=off"]}
 ARCH = os.environ.get("NPGX_OFFLOAD_ARCH", "gfx950")
 
 
@@ -39,7 +42,8 @@ def build(force=False, verbose=False, profile=False, lib_path=None, defines=()):
         stem, ext = os.path.splitext(src)
         obj = os.path.join(CSRC, stem + ("_prof.o" if profile else ".o"))
         if ext == ".cpp":  # host-only helpers
-            cmd = ["g++", "-c", "-O2", "-std=c++17", "-fPIC", "-o", obj, os.path.join(CSRC, src)]
+            cmd = ["g++", "-c", "-O2", "-std=c++17", "-fPIC"] + HOST_FLAGS.get(src, []) + \
+                  ["-o", obj, os.path.join(CSRC, src)]
         else:
             cmd = ["hipcc", "-c", "-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH,
                    "-munsafe-fp-atomics", "-Wno-unused-result", "-I", os.path.join(os.path.dirname(HERE), "include"),

@@ -41,11 +41,19 @@ class _EngineProcessor(Processor):
         return self.engine_name
 
     def run_impl(self):
-        from . import _capi
-        from .blockset import BlockSetEngine
         bs = self.block_set()
         if not bs.blocks:
             return
+        eng = self.engine_of(bs)
+        eng.apply(self.engine_processor())
+        bs.blocks = [Block([Fragment(bs.seqs[q], mn, mx, ori, row) for q, mn, mx, ori, row in blk])
+                     for blk in eng.blocks()]
+        self.after_apply(eng, bs)
+
+    def engine_of(self, bs):
+        """An engine holding bs's sequences and blocks."""
+        from . import _capi
+        from .blockset import BlockSetEngine
         known = {id(s) for s in bs.seqs}
         for b in bs.blocks:  # sequences named only by fragments (fragment-only files)
             for f in b.fragments:
@@ -58,10 +66,7 @@ class _EngineProcessor(Processor):
                   for b in bs.blocks]
         ss = _capi.SeqSet([s.data for s in bs.seqs], [s.name for s in bs.seqs])
         eng = BlockSetEngine(ss, **self.engine_kwargs())
-        eng.set_blocks(blocks).apply(self.engine_processor())
-        bs.blocks = [Block([Fragment(bs.seqs[q], mn, mx, ori, row) for q, mn, mx, ori, row in blk])
-                     for blk in eng.blocks()]
-        self.after_apply(eng, bs)
+        return eng.set_blocks(blocks)
 
     def after_apply(self, eng, bs):
         """What a processor takes from the engine besides the blocks."""
@@ -360,6 +365,102 @@ class TrySmth(_EngineProcessor):
     def after_apply(self, eng, bs):
         for b, n in zip(bs.blocks, eng.block_names()):
             b.name = n
+
+
+class _AnalysisProcessor(_EngineProcessor):
+    """A processor that changes no block: the engine computes, the text the
+    reference writes is kept in .text and written to the processor's file
+    option when that names a file."""
+
+    file_opt = None
+    text = ""
+
+    def run_impl(self):
+        bs = self.block_set()
+        eng = self.engine_of(bs)
+        self.text = self.make_text(eng, bs)
+        path = self.opt_value(self.file_opt)
+        if path:
+            with open(path, "w") as f:
+                f.write(self.text)
+
+    @staticmethod
+    def sorted_blocks(bs):
+        """BlocksJobs::sort_blocks (BlocksJobs.cpp:183-193): size descending,
+        alignment length descending, name ascending; ties in the set's order."""
+        return sorted(range(len(bs.blocks)), key=lambda k: (-bs.blocks[k].size(), -bs.blocks[k].alignment_length(),
+                                                            bs.blocks[k].name))
+
+
+@register
+class GlobalTree(_AnalysisProcessor):
+    """GlobalTree (GlobalTree.cpp:27-116): the neighbour-joining tree of the
+    genomes over the stem blocks, bootstraps = diagnostic columns."""
+    name = "GlobalTree"
+    file_opt = "out-global-tree"
+
+    def __init__(self):
+        super().__init__()
+        self.add_opt("out-global-tree", "Output file with global tree", "")
+        self.add_opt("bootstrap-print", "How to print bootstrap values ('no', 'in-braces', 'before-length')",
+                     "before-length")
+        self.add_opt_rule("bootstrap-print is no, in-braces or before-length",
+                          lambda p: p.opt_value("bootstrap-print") in ("no", "in-braces", "before-length"))
+        self.add_opt("tree-pseudo-leafs", "Convert each leaf to short branch", False)
+
+    def engine_processor(self):
+        return "GlobalTree --bootstrap-print=%s --tree-pseudo-leafs=%d" % (
+            self.opt_value("bootstrap-print"), int(bool(self.opt_value("tree-pseudo-leafs"))))
+
+    def make_text(self, eng, bs):
+        return eng.global_tree(self.opt_value("bootstrap-print"), self.opt_value("tree-pseudo-leafs"))[0]
+
+
+@register
+class PrintTree(_AnalysisProcessor):
+    """PrintTree (PrintTree.cpp:22-83): a newick tree of every block."""
+    name = "PrintTree"
+    file_opt = "tree-file"
+
+    def __init__(self):
+        super().__init__()
+        self.add_opt("tree-file", "Output file with trees", "")
+        self.add_opt("tree-method", "Method of tree construction (upgma/nj)", "nj")
+
+    def engine_processor(self):
+        return "PrintTree --tree-method=" + self.opt_value("tree-method")
+
+    def make_text(self, eng, bs):
+        trees = eng.block_trees(self.opt_value("tree-method"))
+        return "block\tnewick_tree\n" + "".join("%s\t%s\n" % (bs.blocks[k].name, trees[k][0])
+                                                for k in self.sorted_blocks(bs))
+
+
+@register
+class FragmentDistance(_AnalysisProcessor):
+    """FragmentDistance (FragmentDistance.cpp:75-97): the distance of every
+    pair of fragments of every block."""
+    name = "FragmentDistance"
+    file_opt = "distance-file"
+
+    def __init__(self):
+        super().__init__()
+        self.add_opt("distance-file", "Output file with distances", "")
+
+    def engine_processor(self):
+        return "FragmentDistance"
+
+    def make_text(self, eng, bs):
+        pen = eng.pair_distances()
+        out = ["block\tfr.1\tfr.2\tdistance\n"]
+        for k in self.sorted_blocks(bs):
+            b = bs.blocks[k]
+            p, total = iter(pen[k]), b.alignment_length()
+            for i in range(b.size()):
+                for j in range(i + 1, b.size()):
+                    out.append("%s\t%s\t%s\t%g\n" % (b.name, b.fragments[i].id(), b.fragments[j].id(),
+                                                     float(next(p)) / float(total)))
+        return "".join(out)
 
 
 @register
