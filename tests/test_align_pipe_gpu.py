@@ -2,7 +2,8 @@
 CutGaps (permissive and strict), SelfOverlapsResolver, LiteAlign and Align,
 fragments and rows bit-exact vs the oracle -- on the reference's own cases
 (test-script/cut_gaps*, src/test/move_gaps.cpp, src/test/hit.cpp), on random
-gapped blocks, and on DraftPangenome results."""
+gapped blocks, and on DraftPangenome results.  The seams and edges of the
+MoveGaps / CutGaps kernels themselves are in test_gap_shapes_gpu.py."""
 import os
 
 import numpy as np
