@@ -130,6 +130,10 @@ typedef struct {
  * processor instance cached by MetaProcessor (MetaProcessor.cpp:32-38). */
 int npgx_af_create(const npgx_af_options* o, npgx_af** out);
 int npgx_af_run(npgx_af* af, const npgx_seqset* s);
+/* After a run whose host result is deferred (DraftPangenome's device anchors on
+ * one GPU) n_found_frags is not counted until it is asked for here: the count
+ * reads the run's windows again, so the sequence set of that run must still
+ * exist at this call.  The next run on the handle ends the obligation. */
 int npgx_af_stats_get(const npgx_af* af, npgx_af_stats* out);
 /* Result of the last run, in reference order: blocks in FoundFragment (hash)
  * order, fragments inside a block by (sequence rank, direct before reverse,

@@ -47,6 +47,9 @@ class AnchorFinder(Processor):
         self.bloom_params = bloom_params
         self._h = None
         self._h_key = None
+        # the sequence set of the last run: a deferred result's statistics
+        # (npgx_af_stats_get) read its windows again
+        self._last_set = None
         self.stats = None
 
     def _handle(self):
@@ -77,6 +80,7 @@ class AnchorFinder(Processor):
         """Runs the engine on a device sequence set; returns the SoA result."""
         L = _capi.lib()
         h = self._handle()
+        self._last_set = seqset
         _capi.check(L.npgx_af_run(h, seqset.handle))
         return self.result()
 
@@ -86,6 +90,7 @@ class AnchorFinder(Processor):
         find() on one GPU."""
         L = _capi.lib()
         h = self._handle()
+        self._last_set = seqset
         rc = L.npgx_af_run_sharded(h, seqset.handle, comm.pointer())
         if rc != 0 and comm.errors:
             raise _capi.NpgxError(rc, "; ".join(comm.errors))

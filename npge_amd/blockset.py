@@ -243,6 +243,8 @@ class BlockSetEngine:
     def apply(self, processor, af=None):
         L = _capi.lib()
         afh = af._handle() if af is not None else None
+        if af is not None:
+            af._last_set = self.ss  # (its deferred statistics read the set again)
         _capi.check(L.npgx_blockset_apply(self._h, processor.encode(), afh))
         return self
 

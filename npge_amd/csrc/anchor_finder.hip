@@ -14,13 +14,21 @@
 //                   collected(p) = found(p) && !(similar && found(p-1));
 //                   workgroup compaction of collected hashes (one atomic per WG)
 //   sort + unique   H = sorted unique collected hashes (rocPRIM radix sort)
-//   k_table_insert  open-addressing table hash -> index in H
+//   k_table_insert  open-addressing table hash -> index in H, over the
+//                   L = min(|H|, max-anchor-fragments + 1) smallest hashes: the
+//                   only ones that can hold a kept FoundFragment
+//   k_ff_collect    every valid window whose hash is among them ->
+//                   (idx << B) | key2, where key2 = 2*order_off(rank) + pos
+//                   (+size if reverse) orders by (rank, direct before reverse,
+//                   pos) -- FoundFragment's order
+//   radix sort      over the candidate keys, truncate (the cut G = group of the
+//                   last kept key + 1), group on the host.
+// The FoundFragment total over all of H (a statistic) is counted apart
+// (k_ff_count over the table of all of H), at once or when asked for.
+// Sharded runs count first and scatter the kept groups:
 //   k_ff_count      count[idx(h)]++ for every valid window whose hash is in H
 //   exclusive scan  offsets; cut G = #groups starting before max-anchor-fragments
-//   k_ff_scatter    windows of the first G groups -> (idx << B) | key2, where
-//                   key2 = 2*order_off(rank) + pos (+size if reverse) orders by
-//                   (rank, direct before reverse, pos) -- FoundFragment's order
-//   radix sort      over the candidate keys, truncate, group on the host.
+//   k_ff_scatter    windows of the first G groups -> their keys at offsets[idx]
 //
 // Windows are read straight from the 2-bit packed words: the window [p, p+k) is
 // bits [2p, 2p+2k) of the sequence's bit stream, which IS make_hash's value
@@ -582,6 +590,40 @@ __global__ __launch_bounds__(WG) void k_ff_scatter(AfArgs a, TableArgs t, const 
     cand[slot] = ((uint64_t)idx << key_bits) | key2;
 }
 
+// Pass 2 of a run on one GPU, one pass over the windows.  Every hash of H has
+// a FoundFragment (the window that put it there), so group g starts at
+// element >= g of the (hash, position) order and only the L = min(nH,
+// max_anchor_fragments + 1) smallest hashes can hold one of the first
+// max_anchor_fragments elements: the table t holds H[0..L) alone (it fits
+// the caches), a window above H[L-1] ends at one compare, and the members'
+// keys -- k_ff_scatter's -- are appended (their order is the sort's business;
+// segments and counters as in k_found_collect_f, packed by k_seg_compact).
+__global__ __launch_bounds__(WG) void k_ff_collect(AfArgs a, TableArgs t, const uint64_t* __restrict__ H, int64_t L,
+                                                   int key_bits, uint64_t* __restrict__ out,
+                                                   unsigned long long* __restrict__ n_out) {
+    const Chunk c = a.chunks[blockIdx.x];
+    const SeqMeta s = a.meta[c.seq];
+    const int64_t p = c.pos + threadIdx.x;
+    bool col = false;
+    uint64_t key = 0;
+    uint64_t dir;
+    if (p + a.k <= s.size && load_window(a, s, p, dir)) {
+        const uint64_t rev = revcomp(dir, a.k);
+        const uint64_t h = dir < rev ? dir : rev;
+        if (h <= H[L - 1]) {
+            const int64_t idx = table_find(t, h);
+            if (idx >= 0) {
+                // (pos and strand as in k_ff_scatter)
+                const uint64_t pos2 = (uint64_t)p + (h == dir ? 0ull : (uint64_t)s.size);
+                key = ((uint64_t)idx << key_bits) | (2ull * s.order_off + pos2);
+                col = true;
+            }
+        }
+    }
+    const int64_t seg = (int64_t)blockIdx.x % a.nseg;
+    wg_append(col, key, out + seg * a.seg_cap, n_out + seg * 16);
+}
+
 // uint32 <-> order-preserving int32 (x ^ 2^31), so a signed MIN collective over
 // ranks is the unsigned MIN of first-setter orders (0xFFFFFFFF = "never set").
 __global__ void k_flip_sign(uint32_t* __restrict__ v, int64_t n) {
@@ -667,6 +709,14 @@ struct npgx_af {
     std::vector<int32_t> d_by_rank_host;  // what d_by_rank holds (uploaded when the sequence set changes)
     bool d_by_rank_valid = false;
     int64_t regroups = 0;  // deferred results grouped on the host (npgx_af_stats.host_regroups)
+    // A deferred run on one GPU does not count the FoundFragments of the
+    // groups past the cut (n_found_frags = -1): npgx_af_stats_get counts them
+    // when asked, over the run's windows (f_A points into the run's sequence
+    // set, which the caller keeps until then) and its H, still in huniq.  The
+    // next run drops the obligation.
+    bool found_pending = false;
+    AfArgs f_A{};
+    int64_t f_nchunks = 0, f_windows = 0, f_nH = 0;
 
     void ensure_temp(size_t bytes) { temp.ensure(bytes); }
 };
@@ -744,11 +794,73 @@ static void comm_check(int rc, const char* what) {
     if (rc != 0) throw Error(NPGX_ERR_ARG, std::string("collective callback failed: ") + what);
 }
 
+// The membership table over the first n hashes of huniq: sized, its buffers
+// ensured and their resets added to `fills` (launched by the caller with its own).
+static TableArgs af_table_prepare(npgx_af* af, int64_t n, Fills& fills) {
+    uint64_t cap = 1024;
+    // at least 4 slots per hash (NPGX_AF_TABLE_SLOTS overrides): a
+    // non-member window reads a slot line only when its home slot is
+    // taken -- C3 ff_count 0.82 -> 0.63 ms from 2 to 4 slots, C5
+    // 6.9 -> 6.1 ms (`profiles/r03y_table_slots.txt`)
+    static const uint64_t spf = getenv("NPGX_AF_TABLE_SLOTS") ? std::max(2, atoi(getenv("NPGX_AF_TABLE_SLOTS"))) : 4;
+    while (cap < spf * (uint64_t)n) cap <<= 1;
+    NPGX_REQUIRE(cap <= (1ull << 31), NPGX_ERR_RANGE, "hash set too large");
+    int log2cap = 0;
+    while ((1ull << log2cap) < cap) log2cap++;
+    af->tslots.ensure(cap);
+    af->tocc.ensure((size_t)(cap + 31) / 32);
+    fills.add(af->tslots.p, (int64_t)(cap * sizeof(TableSlot)), 0xFFFFFFFFu);
+    fills.add(af->tocc.p, (int64_t)(cap + 31) / 32 * 4, 0u);
+    return TableArgs{af->tslots.p, af->tocc.p, (uint32_t)(cap - 1), 64 - log2cap};
+}
+
+static void af_table_insert(npgx_af* af, const TableArgs& T, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(k_table_insert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, af->huniq.p, n,
+                       af->tslots.p, af->tocc.p, T.mask, T.shift);
+    NPGX_HIP(hipGetLastError());
+}
+
+// FoundFragments of every hash of H (npgx_af_stats.n_found_frags) for a run on
+// one GPU, whose pass 2 looks at the groups the cut can keep alone: the table
+// over all of H, k_ff_count over every window, the scan; the total goes to
+// h_pinned[6] (k_find_cut's third value), valid after the caller's stream_wait.
+static void af_found_total_enqueue(npgx_af* af, const AfArgs& A, int64_t nchunks, int64_t windows, int64_t nH) {
+    hipStream_t st = af->stream;
+    Fills fills;
+    const TableArgs T = af_table_prepare(af, nH, fills);
+    af->counts.ensure((size_t)nH);
+    af->offsets.ensure((size_t)nH);
+    size_t ti = af->timer.begin("table_insert", st, nH * 8.0 + nH * 12.0, nH);
+    fills.add(af->counts.p, nH * 4, 0u);
+    fills.launch(st);
+    NPGX_HIP(hipGetLastError());
+    af_table_insert(af, T, nH, st);
+    af->timer.end(ti, st);
+    ti = af->timer.begin("ff_count", st, windows * (0.375 + 12.0), windows);
+    hipLaunchKernelGGL(k_ff_count, dim3((unsigned)nchunks), dim3(WG), 0, st, A, T, af->counts.p);
+    NPGX_HIP(hipGetLastError());
+    af->timer.end(ti, st);
+    size_t b3 = 0;
+    NPGX_HIP(rocprim::exclusive_scan(nullptr, b3, af->counts.p, af->offsets.p, 0u, (size_t)nH,
+                                     rocprim::plus<uint32_t>(), st));
+    af->ensure_temp(b3);
+    ti = af->timer.begin("scan_cut", st, nH * 8.0, nH);
+    NPGX_HIP(rocprim::exclusive_scan(af->temp.p, b3, af->counts.p, af->offsets.p, 0u, (size_t)nH,
+                                     rocprim::plus<uint32_t>(), st));
+    af->cut.ensure(4);
+    hipLaunchKernelGGL(k_find_cut, dim3(1), dim3(64), 0, st, af->offsets.p, af->counts.p, nH,
+                       (uint64_t)af->opt.max_anchor_fragments, af->cut.p);
+    NPGX_HIP(hipGetLastError());
+    af->timer.end(ti, st);
+    NPGX_HIP(hipMemcpyAsync(af->h_pinned + 4, af->cut.p, 3 * 8, hipMemcpyDeviceToHost, st));
+}
+
 static void af_group_host(npgx_af* af, const std::vector<uint64_t>& keys, const std::vector<uint64_t>& Hh,
                           int key_bits, int32_t R, const SeqMeta* meta, const int32_t* by_rank, int k,
                           bool add_used);
 static void af_materialize(npgx_af* af);
 static void af_pending_used(npgx_af* af);
+static void af_found_pending(npgx_af* af);
 
 static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
     static const bool hdbg = getenv("NPGX_AF_DEBUG") != nullptr;  // host phase times to stderr
@@ -765,6 +877,7 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
         if (af->pending_used) af_pending_used(af);
         af->pending = false;
     }
+    af->found_pending = false;  // (nor is its FoundFragment total owed any longer)
     af->timer.reset();
     af->has_result = false;
     npgx_af_stats& S = af->stats;
@@ -1114,35 +1227,119 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
     Hh.clear();
     uint64_t G = 0;
     int key_bits = bits_for(2ull * order);
-    if (nH > 0) {
-        // --- membership table
-        uint64_t cap = 1024;
-        // at least 4 slots per hash (NPGX_AF_TABLE_SLOTS overrides): a
-        // non-member window reads a slot line only when its home slot is
-        // taken -- C3 ff_count 0.82 -> 0.63 ms from 2 to 4 slots, C5
-        // 6.9 -> 6.1 ms (`profiles/r03y_table_slots.txt`)
-        static const uint64_t spf = getenv("NPGX_AF_TABLE_SLOTS") ? std::max(2, atoi(getenv("NPGX_AF_TABLE_SLOTS"))) : 4;
-        while (cap < spf * (uint64_t)nH) cap <<= 1;
-        NPGX_REQUIRE(cap <= (1ull << 31), NPGX_ERR_RANGE, "hash set too large");
-        int log2cap = 0;
-        while ((1ull << log2cap) < cap) log2cap++;
-        af->tslots.ensure(cap);
-        af->tocc.ensure((size_t)(cap + 31) / 32);
-        TableArgs T{af->tslots.p, af->tocc.p, (uint32_t)(cap - 1), 64 - log2cap};
-        ti = af->timer.begin("table_insert", st, nH * 8.0 + nH * 12.0, nH);
+    if (nH > 0 && !comm) {
+        // --- pass 2 on one GPU: the windows of the L smallest hashes of H
+        // (k_ff_collect), sorted, then the cut: the first keep keys, and
+        // G = the group of the last of them + 1.  The same (G, keep) as the
+        // counting path below: the group holding element max_frag - 1 is the
+        // last one starting before max_frag; the groups below L are complete
+        // in the buffer; and with fewer than max_frag keys L = nH (otherwise
+        // keys >= L = max_frag + 1).  The keys are distinct, so the sorted
+        // order does not depend on the order of the appends.
+        const uint64_t max_frag = (uint64_t)af->opt.max_anchor_fragments;
+        const int64_t L = (int64_t)std::min<uint64_t>((uint64_t)nH, max_frag + 1);
+        const int idx_bits = bits_for((uint64_t)L);
+        NPGX_REQUIRE(idx_bits + key_bits <= 64, NPGX_ERR_RANGE, "FoundFragment sort key does not fit 64 bits");
+        const TableArgs T = af_table_prepare(af, L, fills);
+        ti = af->timer.begin("table_insert", st, L * 8.0 + L * 12.0, L);
+        fills.add(af->segctr.p, (int64_t)A.nseg * 16 * 8, 0u);
+        fills.launch(st);
+        NPGX_HIP(hipGetLastError());
+        af_table_insert(af, T, L, st);
+        af->timer.end(ti, st);
+        // the keys go where pass 1 collected (hseg, packed into hraw: both
+        // hold every window of the run and are free since sort_unique)
+        ti = af->timer.begin("ff_collect", st, local_windows * 0.375, local_windows);
+        hipLaunchKernelGGL(k_ff_collect, grid, block, 0, st, A, T, af->huniq.p, L, key_bits, af->hseg.p,
+                           af->segctr.p);
+        NPGX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_seg_compact, dim3((unsigned)A.nseg), dim3(256), 0, st, af->hseg.p, af->segctr.p,
+                           A.nseg, A.seg_cap, af->hraw.p, af->counters.p + 2);
+        NPGX_HIP(hipGetLastError());
+        af->timer.end(ti, st);
+        NPGX_HIP(hipMemcpyAsync(hp, af->counters.p + 2, 8, hipMemcpyDeviceToHost, st));
+        NPGX_HIP(stream_wait(st));
+        const uint64_t n_keys = hp[0];
+        const uint64_t keep = std::min<uint64_t>(n_keys, max_frag);
+        if (keep > 0) {
+            af->cand_sorted.ensure(n_keys);
+            size_t b4 = 0;
+            const unsigned end_bit = (unsigned)(idx_bits + key_bits);
+            NPGX_HIP(rocprim::radix_sort_keys(nullptr, b4, af->hraw.p, af->cand_sorted.p, (size_t)n_keys, 0u,
+                                              end_bit, st));
+            af->ensure_temp(b4);
+            ti = af->timer.begin("ff_sort", st, n_keys * 32.0, (int64_t)n_keys);
+            NPGX_HIP(rocprim::radix_sort_keys(af->temp.p, b4, af->hraw.p, af->cand_sorted.p, (size_t)n_keys, 0u,
+                                              end_bit, st));
+            af->timer.end(ti, st);
+            NPGX_HIP(hipMemcpyAsync(hp + 1, af->cand_sorted.p + (keep - 1), 8, hipMemcpyDeviceToHost, st));
+        }
+        if (af->defer_host && keep > 0) {  // the keys stay on the device (af_device_keys)
+            af->p_by_rank.assign(ss->by_rank.begin(), ss->by_rank.begin() + R);
+            // the rank table depends only on the sequence set: uploaded when it changes
+            if (!af->d_by_rank_valid || af->d_by_rank_host != af->p_by_rank) {
+                af->d_by_rank_valid = false;
+                af->d_by_rank.ensure((size_t)std::max<int32_t>(R, 1));
+                int32_t* hb = (int32_t*)af->pinned_dl.ensure((size_t)R / 2 + 2);
+                memcpy(hb, af->p_by_rank.data(), (size_t)R * 4);
+                NPGX_HIP(hipMemcpyAsync(af->d_by_rank.p, hb, (size_t)R * 4, hipMemcpyHostToDevice, st));
+                af->d_by_rank_host = af->p_by_rank;
+                af->d_by_rank_valid = true;
+            }
+            // the caller reads the keys on a stream of its own: they are complete when this returns
+            NPGX_HIP(stream_wait(st));
+            G = (hp[1] >> key_bits) + 1;
+            af->pending = true;
+            af->pending_used = true;
+            af->p_keep = (int64_t)keep;
+            af->p_G = G;
+            af->p_key_bits = key_bits;
+            af->p_k = k;
+            af->p_R = R;
+            af->p_meta.assign(meta.begin(), meta.begin() + R);
+            S.n_kept_groups = (int64_t)G;
+            S.n_blocks = S.n_fragments = -1;  // (af_materialize)
+            S.n_found_frags = -1;             // (npgx_af_stats_get)
+            af->found_pending = true;
+            af->f_A = A;
+            af->f_nchunks = nchunks;
+            af->f_windows = local_windows;
+            af->f_nH = nH;
+            af->has_result = true;
+            return;
+        }
+        // a plain run counts the FoundFragments of all of H now
+        af_found_total_enqueue(af, A, nchunks, local_windows, nH);
+        if (keep > 0) {
+            NPGX_HIP(stream_wait(st));
+            G = (hp[1] >> key_bits) + 1;
+            keys.resize(keep);
+            Hh.resize(G);
+            af->pinned_dl.ensure((keep + G) * 8);
+            uint64_t* pk = af->pinned_dl.p;
+            NPGX_HIP(hipMemcpyAsync(pk, af->cand_sorted.p, keep * 8, hipMemcpyDeviceToHost, st));
+            NPGX_HIP(hipMemcpyAsync(pk + keep, af->huniq.p, G * 8, hipMemcpyDeviceToHost, st));
+            NPGX_HIP(stream_wait(st));
+            memcpy(keys.data(), pk, keep * 8);
+            memcpy(Hh.data(), pk + keep, G * 8);
+        } else {
+            NPGX_HIP(stream_wait(st));
+        }
+        S.n_found_frags = (int64_t)hp[6];
+        S.n_kept_groups = (int64_t)G;
+    } else if (nH > 0) {
+        // --- sharded pass 2: FoundFragment counts per hash over the table of
+        // all of H, the cut from their scan, then the kept groups' windows
+        const TableArgs T = af_table_prepare(af, nH, fills);
         af->counts.ensure((size_t)nH);
         af->offsets.ensure((size_t)nH);
         af->cursor.ensure((size_t)nH);
-        fills.add(af->tslots.p, (int64_t)(cap * sizeof(TableSlot)), 0xFFFFFFFFu);
-        fills.add(af->tocc.p, (int64_t)(cap + 31) / 32 * 4, 0u);
+        ti = af->timer.begin("table_insert", st, nH * 8.0 + nH * 12.0, nH);
         fills.add(af->counts.p, nH * 4, 0u);
         fills.add(af->cursor.p, nH * 4, 0u);
         fills.launch(st);
         NPGX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_table_insert, dim3((unsigned)((nH + 255) / 256)), dim3(256), 0, st,
-                           af->huniq.p, nH, af->tslots.p, af->tocc.p, (uint32_t)(cap - 1),
-                           64 - log2cap);
-        NPGX_HIP(hipGetLastError());
+        af_table_insert(af, T, nH, st);
         af->timer.end(ti, st);
 
         // --- pass 2a: FoundFragment counts per hash
@@ -1150,16 +1347,13 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
         if (run_local) hipLaunchKernelGGL(k_ff_count, grid, block, 0, st, A, T, af->counts.p);
         NPGX_HIP(hipGetLastError());
         af->timer.end(ti, st);
-        if (comm) {
-            // exchange 3: global FoundFragment count per hash; keep this rank's own
-            af->counts_local.ensure((size_t)nH);
-            af->offsets_local.ensure((size_t)nH);
-            NPGX_HIP(hipMemcpyAsync(af->counts_local.p, af->counts.p, (size_t)nH * 4,
-                                    hipMemcpyDeviceToDevice, st));
-            NPGX_HIP(stream_wait(st));
-            comm_check(comm->allreduce_i32(comm->user, (int32_t*)af->counts.p, nH, NPGX_OP_SUM),
-                       "allreduce(counts, SUM)");
-        }
+        // exchange 3: global FoundFragment count per hash; keep this rank's own
+        af->counts_local.ensure((size_t)nH);
+        af->offsets_local.ensure((size_t)nH);
+        NPGX_HIP(hipMemcpyAsync(af->counts_local.p, af->counts.p, (size_t)nH * 4, hipMemcpyDeviceToDevice, st));
+        NPGX_HIP(stream_wait(st));
+        comm_check(comm->allreduce_i32(comm->user, (int32_t*)af->counts.p, nH, NPGX_OP_SUM),
+                   "allreduce(counts, SUM)");
         size_t b3 = 0;
         NPGX_HIP(rocprim::exclusive_scan(nullptr, b3, af->counts.p, af->offsets.p, 0u, (size_t)nH,
                                          rocprim::plus<uint32_t>(), st));
@@ -1182,35 +1376,27 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
             const int idx_bits = bits_for(G);
             NPGX_REQUIRE(idx_bits + key_bits <= 64, NPGX_ERR_RANGE,
                          "FoundFragment sort key does not fit 64 bits");
-            // sharded: this rank scatters its own windows by its own offsets
-            uint64_t C_local = C;
-            const uint32_t* scatter_off = af->offsets.p;
-            if (comm) {
-                NPGX_HIP(rocprim::exclusive_scan(af->temp.p, b3, af->counts_local.p, af->offsets_local.p,
-                                                 0u, (size_t)nH, rocprim::plus<uint32_t>(), st));
-                hipLaunchKernelGGL(k_local_cut, dim3(1), dim3(64), 0, st, af->offsets_local.p,
-                                   af->counts_local.p, nH, G, af->cut.p);
-                NPGX_HIP(hipGetLastError());
-                NPGX_HIP(hipMemcpyAsync(hp, af->cut.p + 3, 8, hipMemcpyDeviceToHost, st));
-                NPGX_HIP(stream_wait(st));
-                C_local = hp[0];
-                scatter_off = af->offsets_local.p;
-            }
+            // this rank scatters its own windows by its own offsets
+            NPGX_HIP(rocprim::exclusive_scan(af->temp.p, b3, af->counts_local.p, af->offsets_local.p,
+                                             0u, (size_t)nH, rocprim::plus<uint32_t>(), st));
+            hipLaunchKernelGGL(k_local_cut, dim3(1), dim3(64), 0, st, af->offsets_local.p,
+                               af->counts_local.p, nH, G, af->cut.p);
+            NPGX_HIP(hipGetLastError());
+            NPGX_HIP(hipMemcpyAsync(hp, af->cut.p + 3, 8, hipMemcpyDeviceToHost, st));
+            NPGX_HIP(stream_wait(st));
+            const uint64_t C_local = hp[0];
             af->cand.ensure(std::max<uint64_t>(C_local, 1));
             af->cand_sorted.ensure(C);
             ti = af->timer.begin("ff_scatter", st, local_windows * 0.375 + C_local * 24.0, local_windows);
             if (run_local && C_local > 0)
-                hipLaunchKernelGGL(k_ff_scatter, grid, block, 0, st, A, T, af->huniq.p, G, scatter_off,
+                hipLaunchKernelGGL(k_ff_scatter, grid, block, 0, st, A, T, af->huniq.p, G, af->offsets_local.p,
                                    af->cursor.p, key_bits, af->cand.p);
             NPGX_HIP(hipGetLastError());
             af->timer.end(ti, st);
-            const uint64_t* sort_in = af->cand.p;
-            if (comm) {
-                // exchange 4: all ranks' FoundFragment keys of the kept groups
-                const int64_t tot = gather_u64(af->cand.p, (int64_t)C_local, "allgatherv(FoundFragments)");
-                NPGX_REQUIRE((uint64_t)tot == C, NPGX_ERR_STATE, "sharded FoundFragment count mismatch");
-                sort_in = af->gathered.p;
-            }
+            // exchange 4: all ranks' FoundFragment keys of the kept groups
+            const int64_t tot = gather_u64(af->cand.p, (int64_t)C_local, "allgatherv(FoundFragments)");
+            NPGX_REQUIRE((uint64_t)tot == C, NPGX_ERR_STATE, "sharded FoundFragment count mismatch");
+            const uint64_t* sort_in = af->gathered.p;
             size_t b4 = 0;
             const unsigned end_bit = (unsigned)(idx_bits + key_bits);
             NPGX_HIP(rocprim::radix_sort_keys(nullptr, b4, sort_in, af->cand_sorted.p, (size_t)C, 0u,
@@ -1221,32 +1407,6 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
                                               0u, end_bit, st));
             af->timer.end(ti, st);
             const uint64_t keep = std::min<uint64_t>(C, (uint64_t)af->opt.max_anchor_fragments);
-            if (af->defer_host && !comm && keep > 0) {  // the keys stay on the device (af_device_keys)
-                af->pending = true;
-                af->pending_used = true;
-                af->p_keep = (int64_t)keep;
-                af->p_G = G;
-                af->p_key_bits = key_bits;
-                af->p_k = k;
-                af->p_R = R;
-                af->p_meta.assign(meta.begin(), meta.begin() + R);
-                af->p_by_rank.assign(ss->by_rank.begin(), ss->by_rank.begin() + R);
-                // the rank table depends only on the sequence set: uploaded when it changes
-                if (!af->d_by_rank_valid || af->d_by_rank_host != af->p_by_rank) {
-                    af->d_by_rank_valid = false;
-                    af->d_by_rank.ensure((size_t)std::max<int32_t>(R, 1));
-                    int32_t* hb = (int32_t*)af->pinned_dl.ensure((size_t)R / 2 + 2);
-                    memcpy(hb, af->p_by_rank.data(), (size_t)R * 4);
-                    NPGX_HIP(hipMemcpyAsync(af->d_by_rank.p, hb, (size_t)R * 4, hipMemcpyHostToDevice, st));
-                    af->d_by_rank_host = af->p_by_rank;
-                    af->d_by_rank_valid = true;
-                }
-                // the caller reads the keys on a stream of its own: they are complete when this returns
-                NPGX_HIP(stream_wait(st));
-                S.n_blocks = S.n_fragments = -1;  // (af_materialize)
-                af->has_result = true;
-                return;
-            }
             keys.resize(keep);
             Hh.resize(G);
             af->pinned_dl.ensure((keep + G) * 8);
@@ -1379,6 +1539,17 @@ static void af_pending_used(npgx_af* af) {
     af->pending_used = false;
 }
 
+// the FoundFragment total a deferred run on one GPU left uncounted (see
+// npgx_af.found_pending): counted now, over the run's sequence set
+static void af_found_pending(npgx_af* af) {
+    if (!af->found_pending) return;
+    NPGX_HIP(hipSetDevice(af->device));
+    af_found_total_enqueue(af, af->f_A, af->f_nchunks, af->f_windows, af->f_nH);
+    NPGX_HIP(stream_wait(af->stream));
+    af->stats.n_found_frags = (int64_t)af->h_pinned[6];
+    af->found_pending = false;
+}
+
 void af_set_defer(npgx_af* af, bool on) { af->defer_host = on; }
 
 bool af_device_keys(npgx_af* af, AfDevKeys* o) {
@@ -1458,6 +1629,7 @@ int npgx_af_stats_get(const npgx_af* af, npgx_af_stats* out) {
         NPGX_REQUIRE(af && out, NPGX_ERR_ARG, "null argument");
         const int64_t regroups = af->regroups;  // (not the grouping this call itself may need)
         af_materialize(const_cast<npgx_af*>(af));
+        af_found_pending(const_cast<npgx_af*>(af));
         *out = af->stats;
         out->host_regroups = regroups;
     });
