@@ -67,13 +67,10 @@ int guard(F&& f) {
     }
 }
 
-// Device (kind 0) and pinned host (kind 1) allocations, optionally through a
-// cache of freed buffers (NPGX_BUF_CACHE=1; seqset.hip: size classes, one
-// device synchronisation before freed buffers are reused, reused device
-// buffers zeroed).  buf_alloc sets *got to the bytes actually held (what
-// buf_free takes back).
-void* buf_alloc(int kind, size_t bytes, size_t* got);
-void buf_free(int kind, void* p, size_t got);
+// Device (kind 0: hipMalloc / hipFree) and pinned host (kind 1: hipHostMalloc /
+// hipHostFree) allocations (seqset.hip).
+void* buf_alloc(int kind, size_t bytes);
+void buf_free(int kind, void* p);
 
 // Growable device buffer (capacity kept across runs so repeated steps do not
 // re-allocate).
@@ -81,22 +78,20 @@ template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;
-    size_t held = 0;  // bytes of the allocation
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { release(); }
     void release() {
-        if (p) buf_free(0, p, held);
+        if (p) buf_free(0, p);
         p = nullptr;
         cap = 0;
-        held = 0;
     }
     T* ensure(size_t n) {
         if (n == 0) n = 1;
         if (n > cap) {
             release();
-            p = (T*)buf_alloc(0, n * sizeof(T), &held);
+            p = (T*)buf_alloc(0, n * sizeof(T));
             cap = n;
         }
         return p;
@@ -106,7 +101,6 @@ struct DevBuf {
     void swap(DevBuf& o) {
         std::swap(p, o.p);
         std::swap(cap, o.cap);
-        std::swap(held, o.held);
     }
 };
 
@@ -115,20 +109,19 @@ template <class T>
 struct PinnedBuf {
     T* p = nullptr;
     size_t cap = 0;
-    size_t held = 0;
     PinnedBuf() = default;
     PinnedBuf(const PinnedBuf&) = delete;
     PinnedBuf& operator=(const PinnedBuf&) = delete;
     ~PinnedBuf() {
-        if (p) buf_free(1, p, held);
+        if (p) buf_free(1, p);
     }
     T* ensure(size_t n) {
         if (n == 0) n = 1;
         if (n > cap) {
-            if (p) buf_free(1, p, held);
+            if (p) buf_free(1, p);
             p = nullptr;
             cap = std::max(n, cap + cap / 2);
-            p = (T*)buf_alloc(1, cap * sizeof(T), &held);
+            p = (T*)buf_alloc(1, cap * sizeof(T));
         }
         return p;
     }
@@ -138,12 +131,12 @@ struct PinnedBuf {
 // is synchronised so every earlier copy from it has completed).
 struct PinnedArena {
     char* p = nullptr;
-    size_t cap = 0, used = 0, held = 0;
+    size_t cap = 0, used = 0;
     PinnedArena() = default;
     PinnedArena(const PinnedArena&) = delete;
     PinnedArena& operator=(const PinnedArena&) = delete;
     ~PinnedArena() {
-        if (p) buf_free(1, p, held);
+        if (p) buf_free(1, p);
     }
     char* take(size_t n, hipStream_t st) {
         n = (n + 63) & ~(size_t)63;
@@ -151,10 +144,10 @@ struct PinnedArena {
             NPGX_HIP(stream_wait(st));
             used = 0;
             if (n > cap) {
-                if (p) buf_free(1, p, held);
+                if (p) buf_free(1, p);
                 p = nullptr;
                 cap = std::max<size_t>(std::max<size_t>(n, 2 * cap), (size_t)1 << 22);
-                p = (char*)buf_alloc(1, cap, &held);
+                p = (char*)buf_alloc(1, cap);
             }
         }
         char* r = p + used;

@@ -46,7 +46,6 @@ struct Params {
     int wf;  // FindLowSimilar weight factor (FindLowSimilar.cpp:56-60)
     int lh;  // try_aligned: shifts searched incrementally before the prefix search (0: never switch)
     int lm;  // ... the prefix search's first prefix (shifts)
-    int llds = 1;  // the prefix search's first prefixes in the LDS word table when they fit (NPGX_LONG_LDS)
 };
 
 // Per-wave scratch (global memory), sized by the host for the batch.
@@ -1100,7 +1099,7 @@ struct ProcT {
         LongOut L;
         L.found = -1;
         L.M = P.lm;
-        if (P.llds && S.ltab_log2 > 0 && 2u * (uint32_t)min(max(P.lm, LW_STEP), max_shift) <= (1u << S.ltab_log2)) {
+        if (S.ltab_log2 > 0 && 2u * (uint32_t)min(max(P.lm, LW_STEP), max_shift) <= (1u << S.ltab_log2)) {
             // the first prefixes in the LDS word table
             L = find_word_long<LdsU64>(v.p, v.len, v.d, pos, w.lane, w.n, P.ac, max_shift, P.lm, S.lwords,
                                        (LdsU64*)S.lkeys, (LdsU64*)S.lmask, S.ltab_log2, lepoch);

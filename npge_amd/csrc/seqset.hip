@@ -17,9 +17,7 @@
 #include <mutex>
 #include <thread>
 #include <memory>
-#include <map>
 #include <numeric>
-#include <tuple>
 
 #include "common.hpp"
 
@@ -162,163 +160,19 @@ hipError_t stream_wait(hipStream_t s) {
     return e;
 }
 
-// ---- buffer cache behind DevBuf / PinnedBuf / PinnedArena (common.hpp)
-//
-// hipFree and hipHostFree synchronise the whole device and unmap; hipMalloc /
-// hipHostMalloc map (and pin) again.  Pipes that build and drop whole block
-// sets per step (AnchorLoopFast's consensus set, the pair job's per-pair sets)
-// paid ~170 frees and a dozen pinned allocations a step for that.  Freed
-// buffers are kept instead, by (kind, device, size class): a freed buffer
-// first waits in `pend` (kernels or copies may still use it); the first
-// allocation that would reuse one synchronises the device once, zeroes the
-// pending device buffers (a fresh allocation reads as zeros) and makes them
-// all reusable.  Size classes: 4 KiB, then 8 steps an octave.  At most
-// 24 GiB of device and 4 GiB of pinned memory are kept; above that buffers
-// are freed as before.  The cache is never torn down (no runtime calls at
-// process exit).  Opt-in (NPGX_BUF_CACHE=1): the whole GPU suite passes with
-// it, but its gain measured within run-to-run noise (C3 + AnchorLoopFast
-// 173.8 against 180.1 ms a step, C3 and the pair job unchanged;
-// gpurun_out/r05av), so the default keeps the runtime's own allocations.
-namespace {
-struct BufCache {
-    using Key = std::tuple<int, int, size_t>;  // kind (0 device, 1 pinned host), device, class bytes
-    std::mutex mu;
-    std::multimap<Key, void*> ready;
-    std::vector<std::pair<Key, void*>> pend;
-    size_t held[2] = {0, 0};
-    const bool on = getenv("NPGX_BUF_CACHE") && atoi(getenv("NPGX_BUF_CACHE")) != 0;
-};
-BufCache& buf_cache() {
-    static BufCache* c = new BufCache;  // (leaked on purpose)
-    return *c;
+// ---- allocations behind DevBuf / PinnedBuf / PinnedArena (common.hpp)
+void* buf_alloc(int kind, size_t bytes) {
+    void* p = nullptr;
+    NPGX_HIP(kind == 0 ? hipMalloc(&p, bytes) : hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    return p;
 }
-constexpr size_t BUF_CACHE_MAX[2] = {24ull << 30, 4ull << 30};
 
-void raw_free(int kind, void* p) {
+void buf_free(int kind, void* p) {
+    if (!p) return;
     if (kind == 0)
         (void)hipFree(p);
     else
         (void)hipHostFree(p);
-}
-hipError_t raw_alloc(int kind, void** p, size_t bytes) {
-    return kind == 0 ? hipMalloc(p, bytes) : hipHostMalloc(p, bytes, hipHostMallocDefault);
-}
-// the pending buffers of device dev (-1: the pinned host buffers) become
-// reusable once that device (every device, for pinned buffers, which any
-// device's copies may still read) has finished its work (caller holds the lock)
-void buf_flush(BufCache& c, int dev) {
-    bool any = false;
-    for (const auto& e : c.pend) any |= std::get<1>(e.first) == dev;
-    if (!any) return;
-    if (dev >= 0) {
-        DeviceGuard g(dev);
-        NPGX_HIP(hipDeviceSynchronize());
-    } else {
-        int nd = 0;
-        NPGX_HIP(hipGetDeviceCount(&nd));
-        for (int d = 0; d < nd; d++) {
-            DeviceGuard g(d);
-            NPGX_HIP(hipDeviceSynchronize());
-        }
-    }
-    DeviceGuard g(dev >= 0 ? dev : 0);  // (the zeroing below runs on the buffers' own device)
-    bool zeroed = false;
-    std::vector<std::pair<BufCache::Key, void*>> keep;
-    for (const auto& e : c.pend) {
-        if (std::get<1>(e.first) != dev) {
-            keep.push_back(e);
-            continue;
-        }
-        if (std::get<0>(e.first) == 0) {
-            NPGX_HIP(hipMemsetAsync(e.second, 0, std::get<2>(e.first), nullptr));
-            zeroed = true;
-        }
-        c.ready.emplace(e.first, e.second);
-    }
-    c.pend.swap(keep);
-    if (zeroed) NPGX_HIP(hipStreamSynchronize(nullptr));
-}
-}  // namespace
-
-size_t buf_class(size_t bytes) {
-    if (bytes <= 4096) return 4096;
-    const int k = 63 - __builtin_clzll((unsigned long long)bytes);
-    const size_t step = (size_t)1 << (k - 3);
-    return (bytes + step - 1) / step * step;
-}
-
-void* buf_alloc(int kind, size_t bytes, size_t* got) {
-    BufCache& c = buf_cache();
-    const size_t cls = c.on ? buf_class(bytes) : bytes;  // (off: the exact size, as before)
-    *got = cls;
-    int dev = -1;  // pinned host buffers are filed under -1: any device may use them
-    if (kind == 0) NPGX_HIP(hipGetDevice(&dev));
-    void* p = nullptr;
-    if (c.on) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        const BufCache::Key key{kind, dev, cls};
-        auto it = c.ready.find(key);
-        if (it == c.ready.end()) {
-            bool pending = false;
-            for (const auto& e : c.pend) pending |= e.first == key;
-            if (pending) {
-                buf_flush(c, dev);
-                it = c.ready.find(key);
-            }
-        }
-        if (it != c.ready.end()) {
-            p = it->second;
-            c.ready.erase(it);
-            c.held[kind] -= cls;
-            return p;
-        }
-    }
-    hipError_t e = raw_alloc(kind, &p, cls);
-    if (e != hipSuccess && c.on) {  // out of memory: give the cache back to the runtime, then retry once
-        (void)hipGetLastError();
-        std::lock_guard<std::mutex> lk(c.mu);
-        buf_flush(c, dev);
-        if (kind == 0) NPGX_HIP(hipSetDevice(dev));
-        for (auto it = c.ready.begin(); it != c.ready.end();) {
-            if (std::get<0>(it->first) == kind && std::get<1>(it->first) == dev) {
-                raw_free(kind, it->second);
-                c.held[kind] -= std::get<2>(it->first);
-                it = c.ready.erase(it);
-            } else {
-                ++it;
-            }
-        }
-        e = raw_alloc(kind, &p, cls);
-    }
-    NPGX_HIP(e);
-    return p;
-}
-
-void buf_free(int kind, void* p, size_t cls) {
-    if (!p) return;
-    BufCache& c = buf_cache();
-    // filed under the device that owns the allocation, not the calling
-    // thread's current device (a set freed from another device's thread)
-    int dev = -1;
-    bool known = kind == 1;
-    if (c.on && kind == 0) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, p) == hipSuccess && a.device >= 0) {
-            dev = a.device;
-            known = true;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    if (c.on && known) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        if (c.held[kind] + cls <= BUF_CACHE_MAX[kind]) {
-            c.pend.emplace_back(BufCache::Key{kind, dev, cls}, p);
-            c.held[kind] += cls;
-            return;
-        }
-    }
-    raw_free(kind, p);
 }
 
 // Rank (size desc, name asc, input index asc), layout and the packed words /

@@ -76,11 +76,11 @@ struct SaSplit {
     int64_t tgt;        // first int of its sync states (K - 1 states x n rows)
     int32_t seg0;       // its first segment task
     int32_t win;        // half-width of the sync word search window
-    int32_t sub;        // -1: the job's own rows; -2: a twin (the job's rows reversed, see
-                        // "Twins"); else the job's sub-job (a bad region) of this index
-    int32_t twin;       // job splits: 1 + index of the job's twin split, 0: none
+    int32_t sub;        // -1: the job's own rows; else the job's sub-job (a bad region) of this index
+    int32_t pad;        // (0)
     int64_t post;       // >= 0: byte offset of k_split_post's global work area (chains too long for LDS)
 };
+static_assert(sizeof(SaSplit) == 40, "SaSplit: the host plan and k_plan_subs fill arrays of these");
 
 // split-state counters (device): the job splits are planned on the host, the
 // sub-job splits by k_plan_subs
@@ -171,10 +171,6 @@ struct SaArgs {
     const int64_t* bits_off;   // ... their first word
     const int32_t* part0;      // per job split: its first k_chain_copy workgroup (n_splits + 1 entries)
     int32_t split_len;         // segment length for a job of 16 rows (0: no splitting)
-    // twins (split jobs' reversed rows, walked beside the jobs): the reversed
-    // copies, at twin_off[row] for the rows of jobs with a twin
-    const char* twin_rows;
-    const int64_t* twin_off;
     // unsplit twins (order[] entries >= UTWIN_BASE, see "Unsplit twins" at
     // align_device): per job the twin's output offset in utw_pool (-1: none),
     // its state (0 running, 1 done, 2 overflowed) and its columns
@@ -1078,11 +1074,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_
 }
 
 // the sub-jobs to retry: failed (columns -1) after their segments' chain or
-// their own run, whole ones only (a twin's stays with its job)
+// their own run
 __global__ void k_sub_retry_list(SaArgs a) {
     const unsigned int n_sub = (unsigned int)a.alloc[1];
     for (unsigned int sn = blockIdx.x * blockDim.x + threadIdx.x; sn < n_sub; sn += gridDim.x * blockDim.x)
-        if (a.sub_res[sn].x < 0 && a.subs[sn].pad >= 0) {
+        if (a.sub_res[sn].x < 0) {
             const unsigned int q = atomicAdd(&a.counters[5], 1u);  // (< n_sub <= max_sub, rq's size)
             if ((int64_t)q < a.max_sub) ((int32_t*)a.rq)[q] = (int32_t)sn;
         }
@@ -1168,6 +1164,12 @@ static constexpr int SPLIT_SPAN = 2 * SPLIT_RMAX + SPLIT_C + 1;  // word positio
 static constexpr int SPLIT_CT = 256;     // LDS table of the candidate words
 static constexpr int SPLIT_KMAX = 1024;  // segments per job at most
 static constexpr int32_t UTWIN_BASE = 1 << 30;  // order[] entries >= this: the twin of unsplit job (entry - UTWIN_BASE)
+// Tasks of a launch within which unsplit twins are added.  C3 kernel traces:
+// with twins in a launch of 1020 jobs its k_align_jobs went 363 -> 547 us
+// (twice the waves, half the LDS each), while launches of 154-386 jobs gained
+// up to a fifth: twins only while the launch keeps to about one wave per SIMD.
+// 768 and 1024 measured level or slower (profiles/r06ae_utwin_task_cap_ab.txt).
+static constexpr int UTWIN_MAX_TASKS = 512;
 #ifndef SA_SPLIT_WAVES
 #define SA_SPLIT_WAVES 8  // (4 -> 8: C3 align -0.2 ms, R3 -0.2 ms; profiles/r06l_aligner_param_sweep.txt)
 #endif
@@ -1200,10 +1202,7 @@ __host__ __device__ __forceinline__ int seg_cap_for(int mx, int k, int K, int wi
 // reversed bad-region row of one of its sub-jobs (in the job's C)
 __device__ __forceinline__ void split_row(const SaArgs& a, const SaSplit& sp, const SaJob& job, int lane,
                                           const char*& p, int& len) {
-    if (sp.sub == -2) {  // a twin: the job's row reversed
-        p = a.twin_rows + a.twin_off[job.row0 + lane];
-        len = a.row_len[job.row0 + lane];
-    } else if (sp.sub < 0) {
+    if (sp.sub < 0) {
         p = a.rows + a.row_off[job.row0 + lane];
         len = a.row_len[job.row0 + lane];
     } else {
@@ -1830,14 +1829,6 @@ __device__ void split_post_body(const SaArgs& a, const SaSplit& sp, G* gm, long 
                     d.out_cap = oc;
                     d.pad = rg.y - rg.x + 1;  // > 0: its rows are k_sub_rows' to write
                     d.out_off = off + pb - by;
-                    if (sp.twin > 0 && rg.x == 0 && rg.y == L0 - 1) {
-                        // the whole job is one bad region: its rows gap-filtered
-                        // and reversed are the job's input rows reversed, whose
-                        // walk the twin has done (k_twin_post takes it over;
-                        // a negative width keeps k_sub_rows / k_plan_subs off)
-                        d.pad = -d.pad;
-                        ((SaSplit*)a.splits)[sp.twin - 1].sub = sn;
-                    }
                     a.subs[sn] = d;
                     jr[ri] = make_int4(rg.x, rg.y, -(sn + 1), rg.w);
                 }
@@ -1874,7 +1865,7 @@ __global__ __launch_bounds__(256) void k_sub_rows(SaArgs a, int rows) {
     const int lane = threadIdx.x & 63;
     for (unsigned long long p = blockIdx.x * 4ull + (threadIdx.x >> 6); p < n_pairs; p += gridDim.x * 4ull) {
         const SaSub d = a.subs[p / rows];
-        if (d.pad <= 0) continue;
+        if (d.pad == 0) continue;  // (k_align_jobs wrote its rows itself)
         const SaJob job = a.jobs[d.job];
         const int r = (int)(p % rows);
         if (r < job.n) {
@@ -1921,7 +1912,6 @@ __global__ __launch_bounds__(256) void k_plan_subs(SaArgs a) {
     unsigned long long* pool_ctr = (unsigned long long*)(a.sctr + SC_POOL_LO);
     for (unsigned int sn = blockIdx.x * blockDim.x + threadIdx.x; sn < n_sub; sn += gridDim.x * blockDim.x) {
         const SaSub d = a.subs[sn];
-        if (d.pad < 0) continue;  // a twin's walk is this sub-job's re-alignment (k_twin_post)
         const SaJob job = a.jobs[d.job];
         const int n = job.n;
         const int* lens = (const int*)(a.pool + d.out_off);
@@ -1952,7 +1942,7 @@ __global__ __launch_bounds__(256) void k_plan_subs(SaArgs a) {
                 sp.seg0 = (int32_t)s0;
                 sp.win = win;
                 sp.sub = (int32_t)sn;
-                sp.twin = 0;
+                sp.pad = 0;
                 sp.post = -1;
                 ((SaSplit*)a.splits)[si] = sp;
             }
@@ -1979,20 +1969,17 @@ __global__ __launch_bounds__(256) void k_plan_subs(SaArgs a) {
 // One workgroup per split sub-job (split index from `first`): the chain of its
 // segments into the sub-job's output (rows of out_cap) and its identical
 // columns (score_of after the re-alignment) -- what k_align_sub writes for a
-// whole sub-job; a chain that overflowed or does not fit: (-1, 0).
-// Twins (k_twin_post, `last` >= 0: the twin splits [first, last)): a twin
-// whose job k_split_post found to be one bad region (sp.sub >= 0) chains into
-// that sub-job's output; when its chain fails the sub-job goes back to the
-// ordinary path (its width restored: k_sub_rows, k_plan_subs, k_align_sub).
-__global__ __launch_bounds__(POST_THREADS) void k_sub_post(SaArgs a, int first, int last_twin) {
+// whole sub-job; a chain that overflowed or does not fit: (-1, 0).  Every
+// split from `first` on must be a sub-job's (sub >= 0: the job splits, sub -1,
+// come before it, and k_plan_subs writes the rest).
+__global__ __launch_bounds__(POST_THREADS) void k_sub_post(SaArgs a, int first) {
     __shared__ int pk[SPLIT_KMAX], pcols[SPLIT_KMAX], pdst[SPLIT_KMAX];
     __shared__ int s_np, s_L, s_fail, s_scan[POST_THREADS / 64];
     const int tid = threadIdx.x;
-    const bool twins = last_twin >= 0;
-    const int last = twins ? last_twin : (int)min(a.sctr[SC_SPLITS], (unsigned int)a.cap_splits);
+    const int last = (int)min(a.sctr[SC_SPLITS], (unsigned int)a.cap_splits);
     for (int si = first + blockIdx.x; si < last; si += gridDim.x) {
         const SaSplit sp = a.splits[si];
-        if (sp.K < 2 || sp.sub < 0) continue;  // (a twin its job did not need)
+        if (sp.K < 2) continue;
         const SaSub d = a.subs[sp.sub];
         const int n = a.jobs[d.job].n;
         __syncthreads();
@@ -2027,10 +2014,7 @@ __global__ __launch_bounds__(POST_THREADS) void k_sub_post(SaArgs a, int first, 
         }
         __syncthreads();
         if (s_fail) {
-            if (tid == 0) {
-                if (twins) a.subs[sp.sub].pad = -d.pad;  // the ordinary re-alignment after all
-                else a.sub_res[sp.sub] = make_int2(-1, 0);
-            }
+            if (tid == 0) a.sub_res[sp.sub] = make_int2(-1, 0);
             continue;
         }
         char* out = (char*)(a.pool + d.out_off + 256);
@@ -2280,9 +2264,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_
         const bool idle = chained && any_lane(w, start < 0);  // no sync state found
         View v0{nullptr, 0, 1};
         if (w.act) {
-            v0.p = (chained && sp.sub == -2 ? a.twin_rows + a.twin_off[job.row0 + lane]
-                                            : a.rows + a.row_off[job.row0 + lane]) + start;
-            v0.len = a.row_len[job.row0 + lane] - start;
+            const int64_t r = job.row0 + lane;
+            v0.p = a.rows + a.row_off[r] + start;
+            v0.len = a.row_len[r] - start;
         }
         if (a.aligner_type == 0 && !idle) {
             // the rows into LDS when they fit: every char(q) of the greedy walk
@@ -2567,19 +2551,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_
     if (lane == 0) atomicMax(a.slot_epoch, epoch);  // the launch's highest epoch
 }
 
-// the reversed copies of the twin jobs' rows (list: their rows' indices)
-__global__ void k_twin_rows(const char* __restrict__ rows, const int64_t* __restrict__ row_off,
-                            const int32_t* __restrict__ row_len, const int32_t* __restrict__ list, int n,
-                            const int64_t* __restrict__ twin_off, char* __restrict__ out) {
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        const int r = list[i];
-        const char* src = rows + row_off[r];
-        const int L = row_len[r];
-        char* d = out + twin_off[r];
-        for (int c = threadIdx.x; c < L; c += blockDim.x) d[c] = src[L - 1 - c];
-    }
-}
-
 struct GatherRow {
     int64_t out_off;    // output byte offset
     int64_t src;        // device address of the aligned row (0: empty row -> gaps)
@@ -2698,38 +2669,21 @@ struct npgx_aligner {
     // only, the round-4 search)
     int long_head = 128;
     int long_m = 512;
-    int long_lds = 1;  // NPGX_LONG_LDS=0: the prefix search on the global word table only (A/B)
-    int64_t waves_many_at = SA_WAVES_MANY_AT;  // NPGX_SA_MANY_AT: tasks past which a launch takes 4 waves a SIMD (A/B)
     // split jobs whose segment rooms for the whole row suffixes take at most
     // this many bytes get them (NPGX_SEG_FULL_MB; 0: the 8-sync-state rooms).
     // R3: the segment overflows (reason 202) go with them; the sub-job
     // overflows that were left (reason 10, gpurun_out/r05m) re-run in the
     // sub-job retry launch
     int64_t seg_full_bytes = 64ll << 20;
-    // twins of the split jobs (NPGX_TWINS: 0 never -- the default: measured at
-    // C3 and C5 the whole-job bad region they serve is rare among split jobs
-    // and their segments slow the launch -- 1 always, -1 in launches with few
-    // tasks): see "Twins" at align_device
-    int twins = 0;
     // unsplit twins (see "Unsplit twins" at align_device): jobs of at least
     // utw_rows rows (0: none; NPGX_UTWINS), while the launch stays within
-    // utw_max_tasks tasks (NPGX_UTWIN_TASKS)
-    // (C3 kernel traces, gpurun_out/r06e: with twins in a launch of 1020
-    // jobs its k_align_jobs went 363 -> 547 us -- twice the waves, half the
-    // LDS each -- while launches of 154-386 jobs gained up to a fifth: twins
-    // only while the launch keeps to about one wave per SIMD)
+    // UTWIN_MAX_TASKS tasks
     int utw_rows = 3;
-    int utw_max_tasks = 512;
     std::vector<int64_t> h_utw_off;
     std::vector<int32_t> h_utw_q;
     DevBuf<unsigned char> d_utw_pool;
     DevBuf<int64_t> d_utw_off;
     DevBuf<int32_t> d_utw_st;
-    std::vector<int64_t> h_twin_off;
-    std::vector<int32_t> h_twin_list;
-    DevBuf<char> d_twin;
-    DevBuf<int64_t> d_twin_off;
-    DevBuf<int32_t> d_twin_list;
     // bytes the per-slot scratch of one launch may take (NPGX_SLOT_BUDGET_MB;
     // default 16 GiB: allocating much more costs seconds on first use)
     int64_t slot_budget = 0;
@@ -2976,7 +2930,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
     const int32_t* const d_rlen = uj ? as->d_row_len : al->d_row_len.p;
     // row i of job j's letters (host)
     auto row_len_at = [&](int32_t j, int i) -> int32_t { return uj ? uj[j].y : ne_len[jobs[j].row0 + i]; };
-    Params P{o.mismatch_check, o.gap_check, o.aligned_check, o.min_length, wf, al->long_head, al->long_m, al->long_lds};
+    Params P{o.mismatch_check, o.gap_check, o.aligned_check, o.min_length, wf, al->long_head, al->long_m};
 
     std::vector<int32_t>& jlen = al->h_jlen;
     std::vector<int32_t>& jstat = al->h_jstat;
@@ -3083,7 +3037,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                 sp.seg0 = (int32_t)segs.size();
                 sp.win = std::min(SPLIT_RMAX, 64 + mx / 128);
                 sp.sub = -1;
-                sp.twin = 0;
+                sp.pad = 0;
                 sp.post = -1;
                 {  // a chain that may outgrow k_split_post's LDS: a global work area
                     const int64_t need = (((int64_t)J.cap + 63) / 64) * 8 + 17ll * (J.cap + 1) + 64;
@@ -3118,60 +3072,6 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                 splits.push_back(sp);
             }
         }
-        // Twins.  fix_bad_regions (SimilarAligner.cpp:428-459) re-aligns a bad
-        // region's rows gap-filtered and reversed; when the whole alignment is
-        // one bad region -- most many-row alignments (at 17 rows and 0.8 %
-        // divergence fewer than 90 % of the columns are identical) -- those
-        // rows are the job's input rows reversed, known before the walk.  In a
-        // launch with few tasks (the last ExtendLoopFast iterations: tens of
-        // long jobs on a GPU of thousands of wave slots) every split job gets
-        // a twin split over its reversed rows whose segments run in the same
-        // k_align_jobs launch; k_split_post hands a whole-job bad region to
-        // the twin (k_twin_post chains it), so the re-alignment no longer
-        // follows the forward walk.  The walk is the same process_seqs either
-        // way (bit-exact); a twin whose chain fails leaves its sub-job to the
-        // ordinary path, an unneeded twin costs only idle slots.
-        const int n_js = (int)splits.size();
-        bool twins = false;
-        if (attempt == 0 && n_js > 0 && al->twins != 0) {
-            const int64_t unsplit = (int64_t)todo.size() - n_js;
-            twins = al->twins > 0 || 2 * (int64_t)segs.size() + unsplit <= 2048;
-        }
-        int64_t twin_bytes = 0;
-        if (twins) {
-            al->h_twin_off.assign(uj ? (size_t)u_rows : ne_len.size(), 0);
-            al->h_twin_list.clear();
-            for (int si = 0; si < n_js; si++) {
-                SaSplit tw = splits[si];
-                const SaJob& J = jobs[tw.job];
-                for (int i = 0; i < J.n; i++) {
-                    al->h_twin_off[J.row0 + i] = twin_bytes;
-                    al->h_twin_list.push_back((int32_t)(J.row0 + i));
-                    twin_bytes += row_len_at(tw.job, i);
-                }
-                const int ti = (int)splits.size();
-                tw.sub = -2;
-                tw.twin = 0;
-                tw.tgt = n_tgt;
-                tw.seg0 = (int32_t)segs.size();
-                tw.post = -1;
-                n_tgt += (int64_t)(tw.K - 1) * J.n;
-                for (int k = 0; k < tw.K; k++) {
-                    SaSeg g;
-                    g.split = ti;
-                    g.k = k;
-                    g.cap = seg_cap_for(jmax[tw.job], k, tw.K, tw.win, J.cap);
-                    g.pad = 0;
-                    g.out = seg_bytes;
-                    seg_bytes += ((int64_t)J.n * g.cap + 255) & ~255ll;
-                    queue.push_back(-(int32_t)segs.size() - 1);
-                    segs.push_back(g);
-                }
-                for (int t = 0; t + 1 < tw.K; t++) ftasks.push_back(make_int2(ti, t));
-                splits[si].twin = ti + 1;
-                splits.push_back(tw);
-            }
-        }
         if (rdbg && attempt == 0) {
             dbg_split.assign(n_jobs, 0);
             for (const SaSplit& sp : splits) dbg_split[sp.job] = 1;
@@ -3193,7 +3093,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         // (k_align_jobs, ahead of the jobs in the queue); a job that finds
         // itself one bad region takes the twin's result, any other leaves it
         // unused.  The walk is the same process_seqs (bit-exact).  Twins are
-        // added while the launch stays within utw_max_tasks tasks.
+        // added while the launch stays within UTWIN_MAX_TASKS tasks.
         int64_t utw_bytes = 0;
         int n_utw = 0;
         std::vector<int64_t>& uoff = al->h_utw_off;
@@ -3201,11 +3101,11 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
             std::vector<int32_t>& tq = al->h_utw_q;
             tq.clear();
             uoff.assign((size_t)n_jobs, -1);
-            // up to utw_max_tasks tasks, and in any launch the heaviest jobs'
+            // up to UTWIN_MAX_TASKS tasks, and in any launch the heaviest jobs'
             // twins that fill the last 256-task step: the LDS share of every
             // workgroup (one per 256 tasks and CU) stays what it was
             const int64_t q = (int64_t)queue.size();
-            const int64_t room = std::max<int64_t>((int64_t)al->utw_max_tasks - q, (q + 255) / 256 * 256 - q);
+            const int64_t room = std::max<int64_t>((int64_t)UTWIN_MAX_TASKS - q, (q + 255) / 256 * 256 - q);
             for (int32_t q : queue) {
                 if ((int64_t)tq.size() >= room) break;
                 if (q < 0 || jobs[q].n < al->utw_rows) continue;
@@ -3241,7 +3141,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         while ((1ull << tlog) < 2ull * (uint64_t)max_n * (uint64_t)(max_len + 1) + 64) tlog++;
         int depth = max_len / std::max(1, o.aligned_check + 1) + 4;
         auto per_slot = [&](uint32_t tl, int dp) { return (20ll << tl) + 1028ll * dp + 17ll * cols_need; };
-        const int wv = nj > al->waves_many_at ? SA_WAVES_MANY : SA_WAVES_PER_EU;  // this launch's waves a SIMD
+        const int wv = nj > SA_WAVES_MANY_AT ? SA_WAVES_MANY : SA_WAVES_PER_EU;  // this launch's waves a SIMD
         size_t slots = (size_t)std::max(1, std::min(nj, 256 * 4 * wv));
         const int64_t mem_budget = std::max<int64_t>(al->slot_budget, 1ll << 22);
         if (attempt == 0)
@@ -3361,10 +3261,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         // budget shrinks as more workgroups must be resident per CU.
         int64_t max_rows = 0;
         for (int32_t j : todo) max_rows = std::max<int64_t>(max_rows, jsum[j]);
-        static const int64_t per_cu_max = getenv("NPGX_SA_PER_CU_MAX") ? std::max(1, atoi(getenv("NPGX_SA_PER_CU_MAX")))
-                                                                       : 4 * SA_WAVES_MANY;  // (A/B: LDS per slot)
-        const int64_t per_cu = std::min<int64_t>(std::min<int64_t>(4 * wv, per_cu_max),
-                                                 std::max<int64_t>(1, ((int64_t)nj + 255) / 256));
+        const int64_t per_cu = std::min<int64_t>(4 * wv, std::max<int64_t>(1, ((int64_t)nj + 255) / 256));
         const int64_t budget = LDS_PER_CU / per_cu;
         // word history of the row-parallel search (HIST_SHIFTS x 64 words) when
         // the budget allows
@@ -3408,8 +3305,6 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         A.ctr1 = as ? al->d_ctr1.p : nullptr;
         A.ftasks = nullptr;
         A.split_len = o.aligner_type == 0 ? al->split : 0;
-        A.twin_rows = nullptr;
-        A.twin_off = nullptr;
         A.utw_off = nullptr;
         A.utw_state = nullptr;
         A.utw_len = nullptr;
@@ -3494,22 +3389,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
             A.qseg = al->d_qseg.p;
             A.qsub = al->d_qsub.p;
             A.ftasks = al->d_ftasks.p;
-            if (twins) {
-                al->d_twin.grow((size_t)std::max<int64_t>(twin_bytes, 1));
-                al->d_twin_off.grow(al->h_twin_off.size());
-                al->d_twin_list.grow(al->h_twin_list.size());
-                put(al->d_twin_off.p, al->h_twin_off.data(), al->h_twin_off.size() * 8);
-                put(al->d_twin_list.p, al->h_twin_list.data(), al->h_twin_list.size() * 4);
-                A.twin_rows = al->d_twin.p;
-                A.twin_off = al->d_twin_off.p;
-            }
             flush();
-            if (twins) {
-                hipLaunchKernelGGL(k_twin_rows, dim3((unsigned)std::min<size_t>(al->h_twin_list.size(), 4096)),
-                                   dim3(256), 0, st, d_rows, d_roff, d_rlen, al->d_twin_list.p,
-                                   (int)al->h_twin_list.size(), al->d_twin_off.p, al->d_twin.p);
-                NPGX_HIP(hipGetLastError());
-            }
             if (n_job_find > 0) {
                 size_t tf = al->timer.begin("align_split", st, 0.0, (int64_t)n_job_find);
                 hipLaunchKernelGGL(k_split_find, dim3((unsigned)n_job_find), dim3(64 * SPLIT_WAVES), SPLIT_LDS, st, A,
@@ -3535,28 +3415,22 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
         al->timer.end(ti, st);
         pmark(7);
         if (!splits.empty()) {  // the split jobs: chain, regions, deferred bad regions
-            // (the job splits only: the twins [n_js, splits.size()) are chained by k_twin_post)
-            ti = al->timer.begin("align_split_chain", st, 0.0, (int64_t)n_js);
-            hipLaunchKernelGGL(k_split_chain, dim3((unsigned)n_js), dim3(POST_THREADS), 0, st, A);
+            ti = al->timer.begin("align_split_chain", st, 0.0, (int64_t)n_job_splits);
+            hipLaunchKernelGGL(k_split_chain, dim3((unsigned)n_job_splits), dim3(POST_THREADS), 0, st, A);
             NPGX_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_chain_copy, dim3((unsigned)part0.back()), dim3(POST_THREADS), 0, st, A, n_js);
+            hipLaunchKernelGGL(k_chain_copy, dim3((unsigned)part0.back()), dim3(POST_THREADS), 0, st, A,
+                               n_job_splits);
             NPGX_HIP(hipGetLastError());
             al->timer.end(ti, st);
-            ti = al->timer.begin("align_split_post", st, 0.0, (int64_t)n_js);
-            hipLaunchKernelGGL(k_split_post, dim3((unsigned)n_js), dim3(REG_THREADS), POST_LDS, st, A,
+            ti = al->timer.begin("align_split_post", st, 0.0, (int64_t)n_job_splits);
+            hipLaunchKernelGGL(k_split_post, dim3((unsigned)n_job_splits), dim3(REG_THREADS), POST_LDS, st, A,
                                (int)POST_LDS);
             NPGX_HIP(hipGetLastError());
-            if (twins) {  // k_twin_post: the twins whose jobs are one bad region
-                const int n_tw = (int)splits.size() - n_js;
-                hipLaunchKernelGGL(k_sub_post, dim3((unsigned)std::min(n_tw, 512)), dim3(POST_THREADS), 0, st, A, n_js,
-                                   (int)splits.size());
-                NPGX_HIP(hipGetLastError());
-            }
             al->timer.end(ti, st);
         }
         if (deferring) {  // the deferred bad regions, then their jobs (no-ops when nothing was deferred)
             // jobs that may have deferred: the split ones and the long ones
-            int64_t n_fin = (int64_t)n_js;
+            int64_t n_fin = (int64_t)n_job_splits;
             int64_t max_rc = 1;
             {
                 std::vector<uint8_t> is_split(n_jobs, 0);
@@ -3592,7 +3466,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
             al->timer.end(ti, st);
             if (split_subs) {  // the split sub-jobs' chains
                 ti = al->timer.begin("align_sub_post", st, 0.0, 0);
-                hipLaunchKernelGGL(k_sub_post, dim3(512), dim3(POST_THREADS), 0, st, A, n_job_splits, -1);
+                hipLaunchKernelGGL(k_sub_post, dim3(512), dim3(POST_THREADS), 0, st, A, n_job_splits);
                 NPGX_HIP(hipGetLastError());
                 al->timer.end(ti, st);
                 // the failed sub-jobs again, whole, at their proven bound (one
@@ -3747,7 +3621,7 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
                             const int32_t j = sb[q].job;
                             if (j < 0 || j >= n_jobs) continue;
                             s_cnt[j]++;
-                            if (sw2[2 * q] <= 0) continue;  // (split: its segments below; a twin's: no run)
+                            if (sw2[2 * q] <= 0) continue;  // (split: its segments below)
                             s_start[j] = std::min(s_start[j], sw2[2 * q]);
                             s_end[j] = std::max(s_end[j], sw2[2 * q + 1]);
                         }
@@ -3840,8 +3714,6 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
             A1.bits_off = nullptr;
             A1.part0 = nullptr;
             A1.split_len = 0;
-            A1.twin_rows = nullptr;
-            A1.twin_off = nullptr;
             A1.utw_off = nullptr;
             A1.utw_state = nullptr;
             A1.utw_len = nullptr;
@@ -4094,20 +3966,12 @@ int npgx_aligner_create(const npgx_align_options* o, npgx_aligner** out) {
         if (sp && *sp) a->split = std::max(0, atoi(sp));
         const char* lh = getenv("NPGX_LONG_HEAD");
         if (lh && *lh) a->long_head = std::max(0, atoi(lh));
-        const char* ll = getenv("NPGX_LONG_LDS");
-        if (ll && *ll) a->long_lds = atoi(ll) != 0;
-        const char* wm = getenv("NPGX_SA_MANY_AT");
-        if (wm && *wm) a->waves_many_at = std::max(0ll, atoll(wm));
         const char* lm = getenv("NPGX_LONG_M");
         if (lm && *lm) a->long_m = std::max(64, atoi(lm));
         const char* sf = getenv("NPGX_SEG_FULL_MB");
         if (sf && *sf) a->seg_full_bytes = (int64_t)std::max(0, atoi(sf)) << 20;
-        const char* tw = getenv("NPGX_TWINS");
-        if (tw && *tw) a->twins = atoi(tw) > 0 ? 1 : (atoi(tw) == 0 ? 0 : -1);
         const char* ut = getenv("NPGX_UTWINS");
         if (ut && *ut) a->utw_rows = std::max(0, atoi(ut));
-        const char* utt = getenv("NPGX_UTWIN_TASKS");
-        if (utt && *utt) a->utw_max_tasks = std::max(0, atoi(utt));
         const char* fc = getenv("NPGX_TEST_FIRST_CAP");
         if (fc && *fc) a->test_first_cap = std::max(0, atoi(fc));
         const char* sb = getenv("NPGX_SLOT_BUDGET_MB");

@@ -192,16 +192,14 @@ def test_split_similar_families(split, monkeypatch):
     _check(jobs)
 
 
-@pytest.mark.parametrize("twins", ["0", "1", "-1"])
 @pytest.mark.parametrize("split", ["128", "384"])
-def test_twins(twins, split, monkeypatch):
-    """Twins (similar_aligner.hip, align_device "Twins"): every split job also
-    walks its reversed rows in the same launch, and a job that turns out to be
-    one bad region takes that walk as its re-alignment (NPGX_TWINS 1: always,
-    0: never, -1: in launches with few tasks).  Families from nearly identical
-    (a good alignment: the twin is not used) to unrelated (one bad region;
-    chains that fail on missed sync states fall back), many rows and two."""
-    monkeypatch.setenv("NPGX_TWINS", twins)
+def test_split_one_bad_region(split, monkeypatch):
+    """Split jobs whose alignment is one bad region as a whole, at short
+    segments.  Families from nearly identical (a good alignment: no bad region)
+    to unrelated (k_split_post finds the whole job one bad region; its rows go
+    through k_sub_rows -> k_plan_subs -> k_sub_post, and a sub-job whose chain
+    fails on missed sync states falls back to the whole re-run), many rows and
+    two."""
     monkeypatch.setenv("NPGX_ALIGN_SPLIT", split)
     rng = np.random.default_rng(41)
     jobs = []
