@@ -23,6 +23,7 @@
 #include <cstring>
 #include <numeric>
 #include <string>
+#include <type_traits>
 
 #include "common.hpp"
 #include "sa_device.hpp"
@@ -181,6 +182,9 @@ struct SaArgs {
     int32_t cap_splits, cap_segs;
     int64_t cap_tgt, cap_find, cap_pool;
 };
+// the host builds one from zero (SaArgs A{}) and passes it by value to every launch
+static_assert(std::is_trivially_copyable<SaArgs>::value, "SaArgs is a kernel argument");
+static_assert(sizeof(SaArgs) == 600,"SaArgs: a new field gets its value in one of align_device's *_args");
 
 // align_device's async mode: job j's status is final (0 / 2: done, 1:
 // overflowed; 3, deferred, is not final) -- called by the one lane that wrote
@@ -2603,6 +2607,44 @@ int weight_factor(int64_t min_identity_x1e4) {
     return (int)(fr < 5000 ? ip : ip + 1);               // Decimal::round
 }
 
+// What sizes an attempt's buffers: its jobs' A|B|C scratch and its largest job
+struct SaBound {
+    int64_t scratch = 0;
+    int max_n = 1, max_len = 1, max_cap = 1;
+};
+
+// align_device's host plan of a batch (the steps that fill it are at
+// align_device).  It lives in the handle: the vectors keep their capacity
+// from call to call.
+struct SaPlan {
+    // plan_batch: the jobs, their non-empty rows, the queue order, the wide jobs
+    std::vector<SaJob> jobs;
+    std::vector<int64_t> ne_off;
+    std::vector<int32_t> ne_len, order, wide_idx;
+    std::vector<int32_t> jsum, jmax;  // residues and longest row per job
+    std::vector<uint8_t> cls, is_wide;
+    std::vector<WideJobIn> wide_in;
+    SaBound first;  // the first attempt's rooms
+    int64_t n_reg = 0, n_sub_max = 0;
+    // the attempt under way: its jobs, its work queue, its results
+    std::vector<int32_t> todo, queue, again, jlen, jstat;
+    // plan_splits (first attempt)
+    std::vector<uint8_t> is_split;
+    std::vector<SaSplit> splits;
+    std::vector<SaSeg> segs;
+    std::vector<int2> ftasks;
+    std::vector<int64_t> bits_off;
+    std::vector<int32_t> part0;
+    int64_t n_tgt = 0, seg_bytes = 0, post_bytes = 0, bits_words = 0;
+    // plan_twins (first attempt)
+    std::vector<int64_t> utw_off;
+    std::vector<int32_t> utw_q;
+    int64_t utw_bytes = 0;
+    int n_utw = 0;
+    // plan_async_rerun: every job at the proven bound
+    std::vector<SaJob> jobs1;
+};
+
 }  // namespace npgx
 
 using namespace npgx;
@@ -2611,13 +2653,7 @@ struct npgx_aligner {
     npgx_align_options opt;
     int device = 0;
     hipStream_t stream = nullptr;
-    // align_device's host arrays (kept for their capacity)
-    std::vector<npgx::SaJob> h_jobs;
-    std::vector<int64_t> h_ne_off;
-    std::vector<int32_t> h_ne_len, h_order, h_jlen, h_jstat;
-    std::vector<double> h_cost;
-    std::vector<int32_t> h_jsum;
-    std::vector<uint8_t> h_cls;
+    SaPlan plan;  // align_device's host arrays (kept for their capacity)
     DevBuf<char> d_rows;
     DevBuf<int64_t> d_row_off;
     DevBuf<int32_t> d_row_len;
@@ -2679,8 +2715,6 @@ struct npgx_aligner {
     // utw_rows rows (0: none; NPGX_UTWINS), while the launch stays within
     // UTWIN_MAX_TASKS tasks
     int utw_rows = 3;
-    std::vector<int64_t> h_utw_off;
-    std::vector<int32_t> h_utw_q;
     DevBuf<unsigned char> d_utw_pool;
     DevBuf<int64_t> d_utw_off;
     DevBuf<int32_t> d_utw_st;
@@ -2691,18 +2725,12 @@ struct npgx_aligner {
     // row + c columns at most, so that alignments with more insertions overflow
     // it and take the re-run at the proven bound (0: off)
     int test_first_cap = 0;
-    std::vector<SaSplit> h_splits;
-    std::vector<SaSeg> h_segs;
-    std::vector<int2> h_ftasks;
-    std::vector<int32_t> h_queue, h_jmax;
     DevBuf<SaSplit> d_splits;
     DevBuf<unsigned char> d_post;  // k_split_post's global work areas
     DevBuf<int4> d_chain, d_chain_hdr;
     DevBuf<unsigned long long> d_chain_bits;
     DevBuf<int64_t> d_bits_off;
     DevBuf<int32_t> d_part0;
-    std::vector<int64_t> h_bits_off;
-    std::vector<int32_t> h_part0;
     DevBuf<SaSeg> d_segs;
     DevBuf<int2> d_ftasks;
     DevBuf<int32_t> d_targets;
@@ -2727,7 +2755,6 @@ struct npgx_aligner {
     std::vector<unsigned char> h_blob;
     DevBuf<unsigned char> d_blob;
     // async mode (AlignAsync): the re-run's jobs, list, counters, flags
-    std::vector<npgx::SaJob> h_jobs1;
     DevBuf<SaJob> d_jobs1;
     DevBuf<int32_t> d_order1, d_ctr1;
     DevBuf<uint8_t> d_retried;
@@ -2736,426 +2763,308 @@ struct npgx_aligner {
 
 namespace npgx {
 
-// Device-resident batch: row r of the batch is d_rows[row_off[r] .. +row_len[r])
-// (host arrays describing device memory).  Results stay on the device: job j's
-// non-empty row k is at res.bptr[j] + k*res.cap[j] for res.len[j] columns.
-void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, const int32_t* row_len,
-                  const int32_t* job_row_start, int32_t n_jobs, AlignResult& res, const AlignAsync* as) {
-    NPGX_HIP(hipSetDevice(al->device));
+// ---- align_device, step by step ("align_device, step by step") ----
 
-    auto tp = std::chrono::steady_clock::now();
-    auto ms = [](std::chrono::steady_clock::time_point t) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-    };
-    hipStream_t st = al->stream;
-    const npgx_align_options& o = al->opt;
-    NPGX_REQUIRE(n_jobs >= 0, NPGX_ERR_ARG, "n_jobs < 0");
-    const int2* uj = as ? as->ujobs : nullptr;  // uniform jobs: no host row arrays
-    const int64_t r_base = (n_jobs && !uj) ? job_row_start[0] : 0;
-    const int64_t n_rows = (n_jobs && !uj) ? (int64_t)job_row_start[n_jobs] - r_base : 0;
-    // host arrays kept in the handle across calls (capacity reused)
-    std::vector<SaJob>& jobs = al->h_jobs;
-    std::vector<int64_t>& ne_off = al->h_ne_off;
-    std::vector<int32_t>& ne_len = al->h_ne_len;
-    jobs.resize(n_jobs);
-    ne_off.clear();
-    ne_len.clear();
-    if (!uj) res.row_ne.assign((size_t)std::max<int64_t>(n_rows, 1), -1);
-    int64_t u_rows = 0;  // (uniform jobs: rows so far)
-    std::vector<double>& cost = al->h_cost;
-    cost.resize(n_jobs);
-    std::vector<int32_t>& jsum = al->h_jsum;  // residues per job
-    jsum.resize(n_jobs);
-    std::vector<int32_t>& jmax = al->h_jmax;  // longest row per job
-    jmax.resize(n_jobs);
-    int64_t scratch = 0, n_reg = 0, n_sub_max = 0;
-    int max_n = 1, max_len = 1, max_cap = 1;
-    std::vector<WideJobIn> wide_in;
-    std::vector<int32_t> wide_idx;
-    const int wf = weight_factor(o.min_identity_x1e4);
-    // after reduce_regions every region but a lone one weighs >= min_length:
-    // at least this many columns wide
-    const int min_width = std::max(1, std::min(o.min_length, (o.min_length + wf - 1) / std::max(wf, 1)));
-    for (int32_t j = 0; j < n_jobs; j++) {
-        SaJob& J = jobs[j];
-        int n = 0;
-        int64_t sum = 0;
-        int mx = 0;
-        if (uj) {
-            const int2 q = uj[j];
-            NPGX_REQUIRE(q.x >= 0 && q.x <= 64 && q.y > 0 && q.y < (1 << 30), NPGX_ERR_RANGE, "uniform job out of range");
-            J.row0 = u_rows;
-            u_rows += q.x;
-            n = q.x;
-            sum = (int64_t)q.x * q.y;
-            mx = q.x ? q.y : 0;
-        }
-        const int64_t r0 = uj ? 0 : job_row_start[j], r1 = uj ? 0 : job_row_start[j + 1];
-        NPGX_REQUIRE(r1 >= r0, NPGX_ERR_ARG, "job_row_start not monotone");
-        if (!uj) J.row0 = (int64_t)ne_len.size();
-        for (int64_t r = r0; r < r1; r++) {
-            const int64_t len = row_len[r];
-            NPGX_REQUIRE(len >= 0 && len < (1ll << 30), NPGX_ERR_RANGE, "row length out of range");
-            if (len == 0) continue;
-            res.row_ne[(size_t)(r - r_base)] = (int64_t)ne_len.size() - J.row0;
-            ne_off.push_back(row_off[r]);
-            ne_len.push_back((int32_t)len);
-            n++;
-            sum += len;
-            mx = std::max<int>(mx, (int)len);
-        }
-        J.n = n;
-        if (n > 64) {  // a wide problem: one workgroup of its own (wide_aligner.hip)
-            wide_in.push_back(WideJobIn{J.row0, n, 0});
-            wide_idx.push_back(j);
-            J.cap = 0;
-            J.scratch = 0;
-            J.reg_off = 0;
-            J.reg_cap = 0;
-            J.pad = 0;
-            cost[j] = 0;
-            jsum[j] = (int32_t)std::min<int64_t>(sum, INT32_MAX);
-            jmax[j] = mx;
-            continue;
-        }
-        // first attempt: 2*max+64 columns (the proven bound is the sum of lengths)
-        int64_t cap = std::min<int64_t>(sum, 2ll * mx + 64);
-        if (o.aligner_type == 1) cap = mx;
-        if (al->test_first_cap > 0) cap = std::min<int64_t>(cap, (int64_t)mx + al->test_first_cap);
-        J.cap = (int32_t)((std::max<int64_t>(cap, 1) + 15) & ~15ll);
-        J.scratch = scratch;
-        scratch += (3ll * n * J.cap + 255) & ~255ll;
-        J.reg_off = n_reg;
-        J.reg_cap = n > 1 ? std::min(J.cap + 1, J.cap / min_width + 2) : 0;
-        J.pad = 0;
-        n_reg += J.reg_cap;
-        n_sub_max += (J.reg_cap + 1) / 2;
-        cost[j] = double(n) * double(sum);
-        jsum[j] = (int32_t)std::min<int64_t>(sum, INT32_MAX);
-        jmax[j] = mx;
-        max_n = std::max(max_n, n);
-        max_len = std::max(max_len, mx);
-        max_cap = std::max<int>(max_cap, J.cap);
-    }
-    static const bool pdbg = getenv("NPGX_PREP_DEBUG") != nullptr;  // host phase times to stderr
+static double ms_since(std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
+// NPGX_PREP_DEBUG: host phase times to stderr
+struct PrepClock {
+    bool on = false;
     double pt[12] = {0};
-    auto pt0 = tp;  // (phase 0: the per-job loop above)
-    auto pmark = [&](int i) {
-        if (!pdbg) return;
-        pt[i] += ms(pt0);
-        pt0 = std::chrono::steady_clock::now();
-    };
-    pmark(0);
-    // heaviest first (rows x residues), by power-of-two cost classes: the order
-    // only balances the load, results do not depend on it
-    std::vector<int32_t>& order = al->h_order;
-    order.resize(n_jobs);
-    {
-        int cnt[65] = {0};
-        std::vector<uint8_t>& cls = al->h_cls;
-        cls.resize(n_jobs);
-        for (int32_t j = 0; j < n_jobs; j++) {
-            const uint64_t c = (uint64_t)cost[j];
-            cls[j] = (uint8_t)(c ? 64 - __builtin_clzll(c) : 0);  // 0..64
-            cnt[cls[j]]++;
-        }
-        int at[65];
-        int acc = 0;
-        for (int c = 64; c >= 0; c--) {
-            at[c] = acc;
-            acc += cnt[c];
-        }
-        for (int32_t j = 0; j < n_jobs; j++) order[at[cls[j]]++] = j;
-        if (!wide_idx.empty()) {  // the wide problems are not in the batched queue
-            std::vector<uint8_t> is_wide(n_jobs, 0);
-            for (int32_t j : wide_idx) is_wide[j] = 1;
-            order.erase(std::remove_if(order.begin(), order.end(), [&](int32_t j) { return is_wide[j] != 0; }),
-                        order.end());
-        }
+    std::chrono::steady_clock::time_point t0;
+    void mark(int i) {
+        if (!on) return;
+        pt[i] += ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
     }
+    void report(int n_jobs, bool async) const {  // (the async path ends after "post")
+        static const char* const phase[11] = {"prep", "order", "puts", "split_plan", "slots", "args", "lds+split",
+                                              "launch", "post", "wait", "results"};
+        if (!on) return;
+        fprintf(stderr, "align_device%s %d jobs:", async ? " async" : "", n_jobs);
+        for (int i = 0; i < (async ? 9 : 11); i++) fprintf(stderr, " %s %.3f", phase[i], pt[i]);
+        fprintf(stderr, " ms\n");
+    }
+};
 
-    pmark(1);
-    al->d_row_off.ensure(ne_off.size());
-    al->d_row_len.ensure(ne_len.size());
-    al->d_jobs.ensure(jobs.size());
-    al->d_order.ensure(order.size());
-    al->d_job_out.ensure(2 * jobs.size() + 1);
-    int32_t* const d_job_len = al->d_job_out.p;
-    int32_t* const d_job_status = d_job_len + jobs.size();
-    uint32_t* const d_slot_epoch = (uint32_t*)(d_job_status + jobs.size());
-    al->d_job_stats.ensure(jobs.size() * NPGX_JOB_STATS);
-    al->job_stats.assign(al->want_stats ? jobs.size() * NPGX_JOB_STATS : 0, 0);
-    al->d_next.ensure(1);
-    // uploads and zeroings are collected and issued together by flush() before
-    // the next launch (one copy + one k_scatter)
-    al->h_ops.clear();
-    al->h_blob.clear();
-    auto put = [&](void* d, const void* h, size_t bytes) {
+// a kernel in the form of the set (long head or not) and of the launch's waves a SIMD
+typedef void (*SaKernel)(SaArgs);
+struct JobsK { template <bool LONG, int W> static SaKernel get() { return k_align_jobs<LONG, W>; } };
+struct SubK { template <bool LONG, int W> static SaKernel get() { return k_align_sub<LONG, W>; } };
+struct FinishK { template <bool LONG, int W> static SaKernel get() { return k_align_finish<LONG>; } };
+template <class K>
+static SaKernel pick(bool long_head, int wv) {
+    const bool many = wv == SA_WAVES_MANY;
+    if (long_head) return many ? K::template get<true, SA_WAVES_MANY>() : K::template get<true, SA_WAVES_PER_EU>();
+    return many ? K::template get<false, SA_WAVES_MANY>() : K::template get<false, SA_WAVES_PER_EU>();
+}
+
+struct SaSlots {
+    uint32_t tlog = 10;  // word-table entries a slot (log2)
+    int depth = 4;       // stack levels a slot
+    int cols = 256;      // region columns a slot
+    size_t n = 1;        // slots: the launch's workgroups
+};
+struct SaLds {
+    int32_t hist_cap = 0, words_bytes = 0, stage_bytes = 0;
+    uint32_t ltab_log2 = 0;
+    size_t lds_bytes = 0;  // the launch's dynamic LDS
+};
+struct SaAttempt {
+    const char* name;            // of its k_align_jobs launch
+    DevBuf<unsigned char>* scr;  // the jobs' A|B|C
+    SaBound b;
+    bool first;  // caps the slots' tables within the budget and may defer bad regions
+};
+struct SaLaunch {  // what an attempt's later steps need of its first
+    SaArgs A;
+    SaBound b;
+    SaSlots s;
+    SaLds lds;
+    int wv;  // waves a SIMD of its k_align_jobs / k_align_sub
+    bool defer, deferring, split_subs;
+};
+
+// One align_device call: what its steps share, and the steps
+struct SaCall {
+    npgx_aligner* al;
+    SaPlan& p;  // al->plan
+    hipStream_t st;
+    const AlignAsync* as;
+    const int2* uj;  // uniform jobs: no host row arrays
+    int32_t n_jobs;
+    const char* d_rows;
+    Params P;
+    std::chrono::steady_clock::time_point tp;  // since when host time is being booked
+    PrepClock clk;
+    // NPGX_RETRY_DEBUG: the re-run jobs (rows, longest row, residues, first room, split or not, final length) to
+    // stderr; the first attempt's room and overflow reason (-job_len)
+    bool rdbg;
+    std::vector<int32_t> rd_cap0, rd_why;
+    const int64_t* d_roff;
+    const int32_t* d_rlen;
+    int32_t *d_job_len, *d_job_status;
+    uint32_t* d_slot_epoch;
+
+    // row i of job j's letters (host)
+    int32_t row_len_at(int32_t j, int i) const { return uj ? uj[j].y : p.ne_len[p.jobs[j].row0 + i]; }
+    // uploads and zeroings are collected and issued together by flush() before the next launch (one copy + one
+    // k_scatter)
+    void put(void* d, const void* h, size_t bytes) {
         if (!bytes) return;
         const size_t at = (al->h_blob.size() + 15) & ~(size_t)15;
         al->h_blob.resize(at + bytes);
         memcpy(al->h_blob.data() + at, h, bytes);
         al->h_ops.push_back(ScatterOp{d, (int64_t)at, (int64_t)bytes});
-    };
-    auto zero = [&](void* d, size_t bytes) { al->h_ops.push_back(ScatterOp{d, -1, (int64_t)bytes}); };
-    // k_align_jobs / k_align_sub in the form of the set (long head or not) and
-    // of the launch's waves a SIMD
-    typedef void (*SaKernel)(SaArgs);
-    auto launch_sa = [&](SaKernel lf, SaKernel sf, SaKernel lm, SaKernel sm, int wv, size_t g, size_t lds,
-                         const SaArgs& X) {
-        const bool lh = al->long_head > 0, many = wv == SA_WAVES_MANY;
-        hipLaunchKernelGGL(lh ? (many ? lm : lf) : (many ? sm : sf), dim3((unsigned)g), dim3(64), lds, st, X);
-    };
-    auto flush = [&]() {
+    }
+    void zero(void* d, size_t bytes) { al->h_ops.push_back(ScatterOp{d, -1, (int64_t)bytes}); }
+    void flush() {
         if (al->h_ops.empty()) return;
         const size_t nop = al->h_ops.size(), head = (nop * sizeof(ScatterOp) + 15) & ~(size_t)15;
         for (ScatterOp& op : al->h_ops)
             if (op.src >= 0) op.src += (int64_t)head;
         const size_t total = head + al->h_blob.size();
-        char* p = al->pinned.take(total, st);
-        memcpy(p, al->h_ops.data(), nop * sizeof(ScatterOp));
-        memcpy(p + head, al->h_blob.data(), al->h_blob.size());
+        char* h = al->pinned.take(total, st);
+        memcpy(h, al->h_ops.data(), nop * sizeof(ScatterOp));
+        memcpy(h + head, al->h_blob.data(), al->h_blob.size());
         al->d_blob.ensure(total);
-        NPGX_HIP(hipMemcpyAsync(al->d_blob.p, p, total, hipMemcpyHostToDevice, st));
+        NPGX_HIP(hipMemcpyAsync(al->d_blob.p, h, total, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_scatter, dim3((unsigned)nop, 16), dim3(256), 0, st, al->d_blob.p, (int)nop);
         NPGX_HIP(hipGetLastError());
         al->h_ops.clear();
         al->h_blob.clear();
-    };
-    if (!uj) {
-        put(al->d_row_off.p, ne_off.data(), ne_off.size() * 8);
-        put(al->d_row_len.p, ne_len.data(), ne_len.size() * 4);
     }
-    const int64_t* const d_roff = uj ? as->d_row_off : al->d_row_off.p;
-    const int32_t* const d_rlen = uj ? as->d_row_len : al->d_row_len.p;
-    // row i of job j's letters (host)
-    auto row_len_at = [&](int32_t j, int i) -> int32_t { return uj ? uj[j].y : ne_len[jobs[j].row0 + i]; };
-    Params P{o.mismatch_check, o.gap_check, o.aligned_check, o.min_length, wf, al->long_head, al->long_m};
+    // a timed step of the stream: StageTimer::key_launch and the benches read the names
+    template <class F>
+    void timed(const char* name, double bytes, int64_t units, F launch) {
+        const size_t t = al->timer.begin(name, st, bytes, units);
+        launch();
+        NPGX_HIP(hipGetLastError());
+        al->timer.end(t, st);
+    }
+    // k_align_jobs / k_align_sub / k_align_finish: one single-wave workgroup a slot
+    template <class K>
+    void launch_sa(int wv, size_t slots, size_t lds, const SaArgs& X) const {
+        hipLaunchKernelGGL(pick<K>(al->long_head > 0, wv), dim3((unsigned)slots), dim3(64), lds, st, X);
+    }
 
-    std::vector<int32_t>& jlen = al->h_jlen;
-    std::vector<int32_t>& jstat = al->h_jstat;
-    jlen.resize(n_jobs);
-    jstat.resize(n_jobs);
-    std::vector<int64_t> jst(al->want_stats ? (size_t)n_jobs * NPGX_JOB_STATS : 0);
-    res.len.assign(n_jobs, 0);
-    res.cap.assign(n_jobs, 0);
-    res.n.assign(n_jobs, 0);
-    res.bptr.assign(n_jobs, nullptr);
-    for (int32_t j = 0; j < n_jobs; j++) res.n[j] = jobs[j].n;
-    std::vector<int32_t> todo = order;
-    // async mode: the re-run at the proven bound is planned now for every job
-    // (the device picks the ones that overflow), and the first attempt's
-    // buffers are sized to hold it too (nothing may be reallocated under the
-    // kernels in flight)
-    int64_t scratch1 = 0;
-    uint32_t tlog1 = 10;
-    int depth1 = 4, cols1 = 256;
-    size_t slots1 = 1;
-    if (as) {
-        NPGX_REQUIRE(wide_idx.empty(), NPGX_ERR_ARG, "align_device async: problems of more than 64 rows");
-        std::vector<SaJob>& j1 = al->h_jobs1;
-        j1 = jobs;
-        int mn = 1, ml = 1, mc = 1;
-        for (int32_t j : order) {
-            SaJob& J = j1[j];
+    // Step 1, the batch plan: per job its non-empty rows (res.row_ne), the first attempt's room and region room,
+    // the wide jobs; then the queue order.
+    void plan_batch(const int64_t* row_off, const int32_t* row_len, const int32_t* job_row_start, AlignResult& res) {
+        const npgx_align_options& o = al->opt;
+        const int64_t r_base = (n_jobs && !uj) ? job_row_start[0] : 0;
+        const int64_t n_rows = (n_jobs && !uj) ? (int64_t)job_row_start[n_jobs] - r_base : 0;
+        p.jobs.resize(n_jobs);
+        p.ne_off.clear();
+        p.ne_len.clear();
+        if (!uj) res.row_ne.assign((size_t)std::max<int64_t>(n_rows, 1), -1);
+        int64_t u_rows = 0;  // (uniform jobs: rows so far)
+        p.cls.resize(n_jobs);
+        p.jsum.resize(n_jobs);
+        p.jmax.resize(n_jobs);
+        p.wide_in.clear();
+        p.wide_idx.clear();
+        p.n_reg = p.n_sub_max = 0;
+        SaBound b;
+        int cnt[65] = {0};  // jobs per cost class
+        // after reduce_regions every region but a lone one weighs >= min_length:
+        // at least this many columns wide
+        const int min_width = std::max(1, std::min(o.min_length, (o.min_length + P.wf - 1) / std::max(P.wf, 1)));
+        for (int32_t j = 0; j < n_jobs; j++) {
+            SaJob& J = p.jobs[j];
+            int n = 0, mx = 0;  // non-empty rows, the longest
+            int64_t sum = 0;
+            if (uj) {
+                const int2 q = uj[j];
+                NPGX_REQUIRE(q.x >= 0 && q.x <= 64 && q.y > 0 && q.y < (1 << 30), NPGX_ERR_RANGE,
+                             "uniform job out of range");
+                J.row0 = u_rows;
+                u_rows += q.x;
+                n = q.x;
+                sum = (int64_t)q.x * q.y;
+                mx = q.x ? q.y : 0;
+            }
+            const int64_t r0 = uj ? 0 : job_row_start[j], r1 = uj ? 0 : job_row_start[j + 1];
+            NPGX_REQUIRE(r1 >= r0, NPGX_ERR_ARG, "job_row_start not monotone");
+            if (!uj) J.row0 = (int64_t)p.ne_len.size();
+            for (int64_t r = r0; r < r1; r++) {
+                const int64_t len = row_len[r];
+                NPGX_REQUIRE(len >= 0 && len < (1ll << 30), NPGX_ERR_RANGE, "row length out of range");
+                if (len == 0) continue;
+                res.row_ne[(size_t)(r - r_base)] = (int64_t)p.ne_len.size() - J.row0;
+                p.ne_off.push_back(row_off[r]);
+                p.ne_len.push_back((int32_t)len);
+                n++;
+                sum += len;
+                mx = std::max<int>(mx, (int)len);
+            }
+            J.n = n;
+            p.jsum[j] = (int32_t)std::min<int64_t>(sum, INT32_MAX);
+            p.jmax[j] = mx;
+            if (n > 64) {  // a wide problem: one workgroup of its own (wide_aligner.hip)
+                p.wide_in.push_back(WideJobIn{J.row0, n, 0});
+                p.wide_idx.push_back(j);
+                J.cap = J.reg_cap = J.pad = 0;
+                J.scratch = J.reg_off = 0;
+                cnt[p.cls[j] = 0]++;
+                continue;
+            }
+            // first attempt: 2*max+64 columns (the proven bound is the sum of lengths)
+            int64_t cap = std::min<int64_t>(sum, 2ll * mx + 64);
+            if (o.aligner_type == 1) cap = mx;
+            if (al->test_first_cap > 0) cap = std::min<int64_t>(cap, (int64_t)mx + al->test_first_cap);
+            J.cap = (int32_t)((std::max<int64_t>(cap, 1) + 15) & ~15ll);
+            J.scratch = b.scratch;
+            b.scratch += (3ll * n * J.cap + 255) & ~255ll;
+            J.reg_off = p.n_reg;
+            J.reg_cap = n > 1 ? std::min(J.cap + 1, J.cap / min_width + 2) : 0;
+            J.pad = 0;
+            p.n_reg += J.reg_cap;
+            p.n_sub_max += (J.reg_cap + 1) / 2;
+            const uint64_t cost = (uint64_t)(double(n) * double(sum));  // rows x residues: its class, 0..64
+            cnt[p.cls[j] = (uint8_t)(cost ? 64 - __builtin_clzll(cost) : 0)]++;
+            b.max_n = std::max(b.max_n, n);
+            b.max_len = std::max(b.max_len, mx);
+            b.max_cap = std::max<int>(b.max_cap, J.cap);
+        }
+        p.first = b;
+        clk.mark(0);
+        // heaviest first (rows x residues), by power-of-two cost classes: the order
+        // only balances the load, results do not depend on it
+        p.order.resize(n_jobs);
+        int at[65], acc = 0;
+        for (int k = 64; k >= 0; k--) {
+            at[k] = acc;
+            acc += cnt[k];
+        }
+        for (int32_t j = 0; j < n_jobs; j++) p.order[at[p.cls[j]]++] = j;
+        if (!p.wide_idx.empty()) {  // the wide problems are not in the batched queue
+            p.is_wide.assign(n_jobs, 0);
+            for (int32_t j : p.wide_idx) p.is_wide[j] = 1;
+            p.order.erase(std::remove_if(p.order.begin(), p.order.end(), [&](int32_t j) { return p.is_wide[j] != 0; }),
+                          p.order.end());
+        }
+        clk.mark(1);
+        // the per-job device arrays, the row arrays' upload and the empty result
+        const size_t n = p.jobs.size();
+        al->d_row_off.ensure(p.ne_off.size());
+        al->d_row_len.ensure(p.ne_len.size());
+        al->d_jobs.ensure(n);
+        al->d_order.ensure(p.order.size());
+        d_job_len = al->d_job_out.ensure(2 * n + 1);
+        d_job_status = d_job_len + n;
+        d_slot_epoch = (uint32_t*)(d_job_status + n);
+        al->d_job_stats.ensure(n * NPGX_JOB_STATS);
+        al->job_stats.assign(al->want_stats ? n * NPGX_JOB_STATS : 0, 0);
+        al->d_next.ensure(1);
+        al->h_ops.clear();
+        al->h_blob.clear();
+        if (!uj) {
+            put(al->d_row_off.p, p.ne_off.data(), p.ne_off.size() * 8);
+            put(al->d_row_len.p, p.ne_len.data(), p.ne_len.size() * 4);
+        }
+        d_roff = uj ? as->d_row_off : al->d_row_off.p;
+        d_rlen = uj ? as->d_row_len : al->d_row_len.p;
+        p.jlen.resize(n);
+        p.jstat.resize(n);
+        res.len.assign(n, 0);
+        res.cap.assign(n, 0);
+        res.n.assign(n, 0);
+        res.bptr.assign(n, nullptr);
+        for (size_t j = 0; j < n; j++) res.n[j] = p.jobs[j].n;
+    }
+
+    // Caps and scratch offsets at the proven bound (every column holds a letter: the sum of the row lengths) for
+    // `list`'s jobs in `jobs`: what a re-run gets
+    SaBound size_proven(std::vector<SaJob>& jobs, const std::vector<int32_t>& list) {
+        SaBound b;
+        for (int32_t j : list) {
+            SaJob& J = jobs[j];
             int64_t sum = 0;
             for (int i = 0; i < J.n; i++) sum += row_len_at(j, i);
             J.cap = (int32_t)((std::max<int64_t>(sum, 1) + 15) & ~15ll);
-            J.scratch = scratch1;
-            scratch1 += (3ll * J.n * J.cap + 255) & ~255ll;
-            mn = std::max(mn, J.n);
-            ml = std::max(ml, jmax[j]);
-            mc = std::max(mc, J.cap);
+            J.scratch = b.scratch;
+            b.scratch += (3ll * J.n * J.cap + 255) & ~255ll;
+            b.max_n = std::max(b.max_n, J.n);
+            b.max_len = std::max(b.max_len, p.jmax[j]);
+            b.max_cap = std::max<int>(b.max_cap, J.cap);
         }
-        while ((1ull << tlog1) < 2ull * (uint64_t)mn * (uint64_t)(ml + 1) + 64) tlog1++;
-        depth1 = ml / std::max(1, o.aligned_check + 1) + 4;
-        cols1 = std::max(256, mc + 1);
-        const int64_t per1 = (20ll << tlog1) + 1028ll * depth1 + 17ll * cols1;
-        slots1 = (size_t)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((int64_t)order.size(), 256),
-                                                                 std::max<int64_t>(al->slot_budget, 1ll << 22) / per1));
-        al->d_scratch2.grow((size_t)std::max<int64_t>(scratch1, 256));
-        al->d_jobs1.ensure(jobs.size());
-        al->d_order1.ensure(std::max<size_t>(jobs.size(), 1));
-        al->d_ctr1.ensure(2);
-        al->d_retried.ensure(std::max<size_t>(jobs.size(), 1));
+        return b;
     }
-    // NPGX_RETRY_DEBUG: the re-run jobs (rows, longest row, residues, first
-    // room, split or not, final length) to stderr
-    static const bool rdbg = getenv("NPGX_RETRY_DEBUG") != nullptr;
-    std::vector<int32_t> dbg_cap0;
-    std::vector<uint8_t> dbg_split;
-    std::vector<int32_t> dbg_why;  // attempt 0's overflow reason (-job_len)
-    for (int attempt = 0; attempt < 2 && !todo.empty(); attempt++) {
-        DevBuf<unsigned char>& scr = attempt == 0 ? al->d_scratch : al->d_scratch2;
-        if (attempt == 1 && rdbg) {
-            dbg_cap0.assign(n_jobs, 0);
-            for (int32_t j : todo) dbg_cap0[j] = jobs[j].cap;
-        }
-        if (attempt == 1) {  // re-run overflowed jobs at the proven bound, in a second scratch
-            scratch = 0;
-            max_cap = 1;
-            max_n = 1;
-            max_len = 1;
-            for (int32_t j : todo) {
-                SaJob& J = jobs[j];
-                max_n = std::max(max_n, J.n);
-                max_len = std::max(max_len, jmax[j]);
-                int64_t sum = 0;
-                for (int i = 0; i < J.n; i++) sum += row_len_at(j, i);
-                J.cap = (int32_t)((std::max<int64_t>(sum, 1) + 15) & ~15ll);
-                J.scratch = scratch;
-                scratch += (3ll * J.n * J.cap + 255) & ~255ll;
-                max_cap = std::max<int>(max_cap, J.cap);
+
+    // Per-slot scratch: the word table (20 B an entry), the append_aligned stack (1028 B a level) and the regions
+    // of unsplit jobs (17 B a column; good_col doubles as 64 ints of scratch, so 256 columns at least).  The
+    // largest job's bounds set the sizes (a call inserts at most rows x (length + 1) words and nests at most length
+    // / (aligned_check + 1) deep).  When `want` slots at those sizes pass the budget, the first attempt caps the
+    // table and the stack (cap_tables) -- a call that would need more ends its walk and marks the job overflowed
+    // (Proc::table_full, the depth check in Proc::run) -- and a re-run takes fewer slots at the full bounds: the
+    // giant alignments of whole-genome blocks (AnchorLoopFast at C4) then cost memory only where they run.
+    SaSlots size_slots(const SaBound& b, int64_t cols, int64_t want, bool cap_tables) {
+        SaSlots s;
+        while ((1ull << s.tlog) < 2ull * (uint64_t)b.max_n * (uint64_t)(b.max_len + 1) + 64) s.tlog++;
+        s.depth = b.max_len / std::max(1, al->opt.aligned_check + 1) + 4;
+        s.cols = (int)cols;
+        auto per_slot = [&]() { return (20ll << s.tlog) + 1028ll * s.depth + 17ll * cols; };
+        const int64_t budget = std::max<int64_t>(al->slot_budget, 1ll << 22);
+        const int64_t n = std::max<int64_t>(1, want);
+        if (cap_tables)
+            while (n * per_slot() > budget && (s.tlog > 16 || s.depth > 512)) {
+                if (s.tlog > 16 && (20ll << s.tlog) >= 1028ll * s.depth) s.tlog--;
+                else s.depth = std::max(512, s.depth / 2);
             }
-        }
-        pmark(2);
-        // the work queue: the segments of the split jobs (heaviest first), then
-        // the other jobs
-        std::vector<SaSplit>& splits = al->h_splits;
-        std::vector<SaSeg>& segs = al->h_segs;
-        std::vector<int2>& ftasks = al->h_ftasks;
-        std::vector<int32_t>& queue = al->h_queue;
-        splits.clear();
-        segs.clear();
-        ftasks.clear();
-        queue.clear();
-        int64_t n_tgt = 0, seg_bytes = 0, post_bytes = 0, bits_words = 0;
-        std::vector<int64_t>& bits_off = al->h_bits_off;
-        std::vector<int32_t>& part0 = al->h_part0;
-        bits_off.clear();
-        part0.assign(1, 0);
-        if (attempt == 0 && o.aligner_type == 0 && al->split > 0) {
-            for (int32_t j : todo) {
-                const SaJob& J = jobs[j];
-                const int mx = jmax[j];
-                const int K = std::min(SPLIT_KMAX, mx / split_len_for(al->split, J.n));
-                if (J.n < 2 || K < 2 || mx < 4 * SPLIT_W) continue;
-                SaSplit sp;
-                sp.job = j;
-                sp.K = K;
-                sp.tgt = n_tgt;
-                sp.seg0 = (int32_t)segs.size();
-                sp.win = std::min(SPLIT_RMAX, 64 + mx / 128);
-                sp.sub = -1;
-                sp.pad = 0;
-                sp.post = -1;
-                {  // a chain that may outgrow k_split_post's LDS: a global work area
-                    const int64_t need = (((int64_t)J.cap + 63) / 64) * 8 + 17ll * (J.cap + 1) + 64;
-                    if (need > (int64_t)POST_LDS) {
-                        sp.post = post_bytes;
-                        post_bytes += (need + 255) & ~255ll;
-                    }
-                    bits_off.push_back(bits_words);  // (unused with a post area)
-                    if (sp.post < 0) bits_words += J.cap / 64 + 1;
-                    part0.push_back(part0.back() + (J.cap + CHAIN_PART - 1) / CHAIN_PART);
-                }
-                n_tgt += (int64_t)(K - 1) * J.n;
-                // rooms for the whole rest of the rows when that stays within
-                // seg_full_bytes for the job: a walk that misses the later
-                // sync states (repeat insertions: R3) then still finishes its
-                // segment instead of overflowing and re-running the job whole
-                int64_t full_bytes = 0;
-                for (int k = 0; k < K; k++) full_bytes += (int64_t)J.n * seg_cap_for(mx, k, K, sp.win, J.cap, true);
-                const bool full = full_bytes <= al->seg_full_bytes;
-                for (int k = 0; k < K; k++) {
-                    SaSeg g;
-                    g.split = (int32_t)splits.size();
-                    g.k = k;
-                    g.cap = seg_cap_for(mx, k, K, sp.win, J.cap, full);
-                    g.pad = 0;
-                    g.out = seg_bytes;
-                    seg_bytes += ((int64_t)J.n * g.cap + 255) & ~255ll;
-                    queue.push_back(-(int32_t)segs.size() - 1);
-                    segs.push_back(g);
-                }
-                for (int t = 0; t + 1 < K; t++) ftasks.push_back(make_int2((int)splits.size(), t));
-                splits.push_back(sp);
-            }
-        }
-        if (rdbg && attempt == 0) {
-            dbg_split.assign(n_jobs, 0);
-            for (const SaSplit& sp : splits) dbg_split[sp.job] = 1;
-        }
-        if (splits.empty()) {
-            queue = todo;
-        } else {
-            std::vector<uint8_t> is_split(n_jobs, 0);
-            for (const SaSplit& sp : splits) is_split[sp.job] = 1;
-            for (int32_t j : todo)
-                if (!is_split[j]) queue.push_back(j);
-        }
-        // Unsplit twins.  Most many-row alignments are one bad region as a
-        // whole (C3: 90 % of the 17-row flank jobs of the first iterations),
-        // and fix_bad_regions (SimilarAligner.cpp:428-459) then re-aligns the
-        // job's rows reversed after its forward walk: half of a launch's
-        // critical path.  Every unsplit job of at least utw_rows rows gets a
-        // twin task that walks its rows reversed in the same launch
-        // (k_align_jobs, ahead of the jobs in the queue); a job that finds
-        // itself one bad region takes the twin's result, any other leaves it
-        // unused.  The walk is the same process_seqs (bit-exact).  Twins are
-        // added while the launch stays within UTWIN_MAX_TASKS tasks.
-        int64_t utw_bytes = 0;
-        int n_utw = 0;
-        std::vector<int64_t>& uoff = al->h_utw_off;
-        if (attempt == 0 && o.aligner_type == 0 && al->utw_rows > 0) {
-            std::vector<int32_t>& tq = al->h_utw_q;
-            tq.clear();
-            uoff.assign((size_t)n_jobs, -1);
-            // up to UTWIN_MAX_TASKS tasks, and in any launch the heaviest jobs'
-            // twins that fill the last 256-task step: the LDS share of every
-            // workgroup (one per 256 tasks and CU) stays what it was
-            const int64_t q = (int64_t)queue.size();
-            const int64_t room = std::max<int64_t>((int64_t)UTWIN_MAX_TASKS - q, (q + 255) / 256 * 256 - q);
-            for (int32_t q : queue) {
-                if ((int64_t)tq.size() >= room) break;
-                if (q < 0 || jobs[q].n < al->utw_rows) continue;
-                uoff[(size_t)q] = utw_bytes;
-                utw_bytes += ((int64_t)jobs[q].n * jobs[q].cap + 255) & ~255ll;
-                tq.push_back(UTWIN_BASE + q);
-            }
-            n_utw = (int)tq.size();
-            if (n_utw) queue.insert(queue.begin(), tq.begin(), tq.end());
-        }
-        const int nj = (int)queue.size();
-        scr.grow((size_t)std::max<int64_t>(scratch, 256));  // (1.5x headroom: batches grow loop by loop)
-        put(al->d_jobs.p, jobs.data(), jobs.size() * sizeof(SaJob));
-        al->d_order.grow(queue.size());
-        put(al->d_order.p, queue.data(), queue.size() * 4);
-        zero(al->d_next.p, 4);
-        pmark(3);
-        // per-slot scratch: the word table (20 B an entry), the append_aligned
-        // stack (1028 B a level) and the regions of unsplit jobs (17 B a
-        // column), for wv waves on each of the 4 SIMDs of the 256
-        // CUs.  The largest job's bounds set the sizes (a call inserts at most
-        // rows x (length + 1) words and nests at most length / (aligned_check
-        // + 1) deep).  When that many slots at those sizes pass the budget,
-        // attempt 0 caps the table and the stack -- a call that would need more
-        // ends its walk and marks the job overflowed (Proc::table_full, the
-        // depth check in Proc::run) -- and attempt 1 runs fewer slots at the
-        // full bounds: the giant alignments of whole-genome blocks
-        // (AnchorLoopFast at C4) then cost memory only where they run.
-        int64_t cols_need = 256;  // good_col doubles as 64 ints of scratch
-        for (int32_t q : queue)
-            if (q >= 0 && q < UTWIN_BASE) cols_need = std::max<int64_t>(cols_need, (int64_t)jobs[q].cap + 1);
-        uint32_t tlog = 10;
-        while ((1ull << tlog) < 2ull * (uint64_t)max_n * (uint64_t)(max_len + 1) + 64) tlog++;
-        int depth = max_len / std::max(1, o.aligned_check + 1) + 4;
-        auto per_slot = [&](uint32_t tl, int dp) { return (20ll << tl) + 1028ll * dp + 17ll * cols_need; };
-        const int wv = nj > SA_WAVES_MANY_AT ? SA_WAVES_MANY : SA_WAVES_PER_EU;  // this launch's waves a SIMD
-        size_t slots = (size_t)std::max(1, std::min(nj, 256 * 4 * wv));
-        const int64_t mem_budget = std::max<int64_t>(al->slot_budget, 1ll << 22);
-        if (attempt == 0)
-            while ((int64_t)slots * per_slot(tlog, depth) > mem_budget && (tlog > 16 || depth > 512)) {
-                if (tlog > 16 && (20ll << tlog) >= 1028ll * depth) tlog--;
-                else depth = std::max(512, depth / 2);
-            }
-        slots = std::max<size_t>(1, std::min<size_t>(slots, (size_t)(mem_budget / per_slot(tlog, depth))));
-        const size_t tcap = (size_t)1 << tlog;
-        // Word tables: epochs only grow from launch to launch (every slot starts
-        // at the last launch's highest epoch + 1), so entries left by earlier
-        // launches never match, whatever the slot layout; the tables are
-        // cleared only when they grow or the 16-bit epochs run out.
-        const size_t tneed = as ? std::max(slots * tcap, slots1 * ((size_t)1 << tlog1)) : slots * tcap;
+        s.n = (size_t)std::max<int64_t>(1, std::min<int64_t>(n, budget / per_slot()));
+        return s;
+    }
+
+    // The slots' buffers for `s` (and `also`: the async re-run's slots, which run under this attempt's kernels, so
+    // nothing may be reallocated for them later). Word tables: epochs only grow from launch to launch (every slot
+    // starts at the last launch's highest epoch + 1), so entries left by earlier launches never match, whatever the
+    // slot layout; the tables are cleared only when they grow or the 16-bit epochs run out.
+    void grow_slot_buffers(const SaSlots& s, const SaSlots* also) {
+        auto need = [&](size_t mine, size_t its) { return also ? std::max(s.n * mine, also->n * its) : s.n * mine; };
+        const size_t tneed = need((size_t)1 << s.tlog, also ? (size_t)1 << also->tlog : 0);
         if (tneed > al->tcap_alloc || al->epoch_base > 0xF000) {
             al->tkeys.grow(tneed);
             al->tmask.grow(tneed);
@@ -3166,648 +3075,734 @@ void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, 
             al->epoch_base = 1;
         }
         zero(d_slot_epoch, 4);
-        const size_t sneed = as ? std::max(slots * depth, slots1 * depth1) : slots * depth;
+        const size_t sneed = need((size_t)s.depth, also ? (size_t)also->depth : 0);
         al->st_p.grow(sneed * 64);
         al->st_len.grow(sneed * 64);
         al->st_pos.grow(sneed * 64);
         al->st_col.grow(sneed);
-        const int slot_cols = (int)cols_need;
-        const size_t cneed = as ? std::max(slots * (size_t)slot_cols, slots1 * (size_t)cols1) : slots * (size_t)slot_cols;
+        const size_t cneed = need((size_t)s.cols, also ? (size_t)also->cols : 0);
         al->regions.grow(cneed);
         al->good_col.grow(cneed);
+    }
 
-        pmark(4);
-        SaArgs A;
+    // Async mode: the re-run at the proven bound is planned beside the first attempt for every job (the device
+    // picks the ones that overflow).  Returns its slots: min(jobs, 256) of them, at the largest job's full bounds.
+    SaSlots plan_async_rerun() {
+        NPGX_REQUIRE(p.wide_idx.empty(), NPGX_ERR_ARG, "align_device async: problems of more than 64 rows");
+        p.jobs1 = p.jobs;
+        const SaBound b1 = size_proven(p.jobs1, p.order);
+        const SaSlots s1 =
+            size_slots(b1, std::max(256, b1.max_cap + 1), std::min<int64_t>((int64_t)p.order.size(), 256), false);
+        al->d_scratch2.grow((size_t)std::max<int64_t>(b1.scratch, 256));
+        al->d_jobs1.ensure(p.jobs.size());
+        al->d_order1.ensure(std::max<size_t>(p.jobs.size(), 1));
+        al->d_ctr1.ensure(2);
+        al->d_retried.ensure(std::max<size_t>(p.jobs.size(), 1));
+        return s1;
+    }
+
+    // The split plan (first attempt): jobs of at least two rows cut every split_len_for columns of their longest
+    // row (SaSplit / SaSeg, the sync-state tasks, the chain bits and k_chain_copy's parts, k_split_post's work
+    // areas), and the work queue: the segments of the split jobs (heaviest first), then the other jobs.
+    void plan_splits() {
+        plan_whole_queue();
+        p.is_split.assign((size_t)n_jobs, 0);
+        if (al->opt.aligner_type != 0 || al->split <= 0) return;
+        p.queue.clear();
+        for (int32_t j : p.todo) {
+            const SaJob& J = p.jobs[j];
+            const int mx = p.jmax[j];
+            const int K = std::min(SPLIT_KMAX, mx / split_len_for(al->split, J.n));
+            if (J.n < 2 || K < 2 || mx < 4 * SPLIT_W) continue;
+            // (job, K, tgt, seg0, win, sub: the job's own rows, pad, post: none)
+            SaSplit sp{j, K, p.n_tgt, (int32_t)p.segs.size(), std::min(SPLIT_RMAX, 64 + mx / 128), -1, 0, -1};
+            // a chain that may outgrow k_split_post's LDS: a global work area
+            const int64_t need = (((int64_t)J.cap + 63) / 64) * 8 + 17ll * (J.cap + 1) + 64;
+            if (need > (int64_t)POST_LDS) {
+                sp.post = p.post_bytes;
+                p.post_bytes += (need + 255) & ~255ll;
+            }
+            p.bits_off.push_back(p.bits_words);  // (unused with a post area)
+            if (sp.post < 0) p.bits_words += J.cap / 64 + 1;
+            p.part0.push_back(p.part0.back() + (J.cap + CHAIN_PART - 1) / CHAIN_PART);
+            p.n_tgt += (int64_t)(K - 1) * J.n;
+            // rooms for the whole rest of the rows when that stays within
+            // seg_full_bytes for the job: a walk that misses the later sync states
+            // (repeat insertions: R3) then still finishes its segment instead of
+            // overflowing and re-running the job whole
+            int64_t full_bytes = 0;
+            for (int k = 0; k < K; k++) full_bytes += (int64_t)J.n * seg_cap_for(mx, k, K, sp.win, J.cap, true);
+            const bool full = full_bytes <= al->seg_full_bytes;
+            for (int k = 0; k < K; k++) {
+                const SaSeg g{(int32_t)p.splits.size(), k, seg_cap_for(mx, k, K, sp.win, J.cap, full), 0, p.seg_bytes};
+                p.seg_bytes += ((int64_t)J.n * g.cap + 255) & ~255ll;
+                p.queue.push_back(-(int32_t)p.segs.size() - 1);
+                p.segs.push_back(g);
+            }
+            for (int t = 0; t + 1 < K; t++) p.ftasks.push_back(make_int2((int)p.splits.size(), t));
+            p.splits.push_back(sp);
+            p.is_split[j] = 1;
+        }
+        for (int32_t j : p.todo)
+            if (!p.is_split[j]) p.queue.push_back(j);
+    }
+
+    // Unsplit twins (first attempt).  Most many-row alignments are one bad region as a whole (C3: 90 % of the
+    // 17-row flank jobs of the first iterations), and fix_bad_regions (SimilarAligner.cpp:428-459) then re-aligns
+    // the job's rows reversed after its forward walk: half of a launch's critical path.  Every unsplit job of at
+    // least utw_rows rows gets a twin task that walks its rows reversed in the same launch (k_align_jobs, ahead of
+    // the jobs in the queue); a job that finds itself one bad region takes the twin's result, any other leaves it
+    // unused.  The walk is the same process_seqs (bit-exact).  Twins are added while the launch stays within
+    // UTWIN_MAX_TASKS tasks.
+    void plan_twins() {  // (after plan_splits: no twins yet)
+        if (al->opt.aligner_type != 0 || al->utw_rows <= 0) return;
+        p.utw_q.clear();
+        p.utw_off.assign((size_t)n_jobs, -1);
+        // up to UTWIN_MAX_TASKS tasks, and in any launch the heaviest jobs' twins
+        // that fill the last 256-task step: the LDS share of every workgroup (one
+        // per 256 tasks and CU) stays what it was
+        const int64_t nq = (int64_t)p.queue.size();
+        const int64_t room = std::max<int64_t>((int64_t)UTWIN_MAX_TASKS - nq, (nq + 255) / 256 * 256 - nq);
+        for (int32_t q : p.queue) {
+            if ((int64_t)p.utw_q.size() >= room) break;
+            if (q < 0 || p.jobs[q].n < al->utw_rows) continue;
+            p.utw_off[(size_t)q] = p.utw_bytes;
+            p.utw_bytes += ((int64_t)p.jobs[q].n * p.jobs[q].cap + 255) & ~255ll;
+            p.utw_q.push_back(UTWIN_BASE + q);
+        }
+        p.n_utw = (int)p.utw_q.size();
+        if (p.n_utw) p.queue.insert(p.queue.begin(), p.utw_q.begin(), p.utw_q.end());
+    }
+
+    // The queue of p.todo's jobs whole, no segments, no twins: a re-run's
+    void plan_whole_queue() {
+        p.splits.clear();
+        p.segs.clear();
+        p.ftasks.clear();
+        p.bits_off.clear();
+        p.part0.assign(1, 0);
+        p.n_tgt = p.seg_bytes = p.post_bytes = p.bits_words = 0;
+        p.utw_bytes = 0;
+        p.n_utw = 0;
+        p.queue = p.todo;
+    }
+
+    // LDS per workgroup: the 64-shift chunk words (vector search, up to VEC_ROWS rows), the word table of the
+    // row-parallel search (more rows: up to half of what is left; 20 B an entry) and the stage for the job's rows.
+    // A workgroup may take all 160 KiB of a CU's LDS; the budget shrinks as more workgroups must be resident per
+    // CU, and the jobs that no longer fit the stage read their rows from global memory.
+    SaLds plan_lds(const SaBound& b, int nj, int wv, int defer) {
+        SaLds l;
+        int64_t max_rows = 0;
+        for (int32_t j : p.todo) max_rows = std::max<int64_t>(max_rows, p.jsum[j]);
+        const int64_t per_cu = std::min<int64_t>(4 * wv, std::max<int64_t>(1, ((int64_t)nj + 255) / 256));
+        const int64_t budget = LDS_PER_CU / per_cu;
+        // word history of the row-parallel search (HIST_SHIFTS x 64 words) when
+        // the budget allows
+        const int64_t hist_bytes = 64 * HIST_SHIFTS * 8;
+        l.hist_cap = (b.max_n > VEC_ROWS && hist_bytes * 4 <= budget) ? HIST_SHIFTS : 0;
+        const int64_t words_bytes = std::max<int64_t>(64 * VEC_ROWS * 8, l.hist_cap ? hist_bytes : 0);
+        l.words_bytes = (int32_t)words_bytes;
+        if (b.max_n > VEC_ROWS)
+            while (l.ltab_log2 < 12 && (20ll << (l.ltab_log2 + 1)) <= (budget - words_bytes) / 2) l.ltab_log2++;
+        // key, row mask and completion shift per entry
+        const int64_t ltab = 1ll << l.ltab_log2;
+        const int table_bytes = (int)(16 * ltab + 8 * ((ltab + 1) / 2) + words_bytes);
+        const int64_t stage_cap = std::max<int64_t>(0, budget - table_bytes);
+        // short jobs keep A|B|C in the stage too (k_align_jobs): size the stage
+        // for the largest such job within the budget
+        int64_t max_need = (max_rows + 15) & ~15ll;
+        for (int32_t j : p.todo) {
+            if (defer != 0 && p.jobs[j].cap >= defer && p.jobs[j].n >= al->defer_rows) continue;
+            const int64_t need = (((int64_t)p.jsum[j] + 15) & ~15ll) + 3ll * p.jobs[j].n * p.jobs[j].cap;
+            if (need <= stage_cap) max_need = std::max(max_need, need);
+        }
+        l.stage_bytes = al->opt.aligner_type == 0 ? (int32_t)std::min<int64_t>(max_need, stage_cap & ~15ll) : 0;
+        l.lds_bytes = (size_t)table_bytes + (size_t)l.stage_bytes;
+        NPGX_REQUIRE(l.stage_bytes >= 0 && l.lds_bytes <= (size_t)LDS_PER_CU, NPGX_ERR_STATE, "LDS budget");
+        return l;
+    }
+
+    // ---- SaArgs, group by group: every field a launch reads gets its value in one of these (the rest stay zero
+    // from SaArgs{}) ----
+    // what every k_align_jobs launch needs: the batch, a job table and queue, a scratch, the slots
+    SaArgs base_args(const SaJob* jobs, const int32_t* order, int32_t n_queue, unsigned int* next_job,
+                     unsigned char* scratch, const SaSlots& s) {
+        SaArgs A{};
         A.rows = d_rows;
         A.row_off = d_roff;
         A.row_len = d_rlen;
-        A.jobs = al->d_jobs.p;
-        A.order = al->d_order.p;
-        A.n_jobs = nj;
-        A.n_jobs_dev = nullptr;
-        A.aligner_type = o.aligner_type;
-        A.scratch = scr.p;
+        A.jobs = jobs;
+        A.order = order;
+        A.n_jobs = n_queue;
+        A.aligner_type = al->opt.aligner_type;
+        A.scratch = scratch;
         A.job_len = d_job_len;
         A.job_status = d_job_status;
-        A.job_stats = al->want_stats ? al->d_job_stats.p : nullptr;
-        A.next_job = al->d_next.p;
+        if (al->want_stats) A.job_stats = al->d_job_stats.p;
+        A.next_job = next_job;
         A.tkeys = al->tkeys.p;
         A.tmask = al->tmask.p;
         A.tdone = al->tdone.p;
-        A.tcap_log2 = tlog;
+        A.tcap_log2 = s.tlog;
         A.slot_epoch = d_slot_epoch;
         A.epoch_base = al->epoch_base;
         A.st_p = al->st_p.p;
         A.st_len = al->st_len.p;
         A.st_pos = al->st_pos.p;
         A.st_col = al->st_col.p;
-        A.st_depth_max = depth;
+        A.st_depth_max = s.depth;
         A.regions = al->regions.p;
         A.good_col = al->good_col.p;
-        A.slot_cols = slot_cols;
+        A.slot_cols = s.cols;
         A.P = P;
-        bool defer = attempt == 0 && al->defer > 0 && o.aligner_type == 0 && n_reg > 0 && max_cap >= al->defer;
-        if (defer) {  // some job long enough and with enough rows
-            defer = false;
-            for (int32_t j : todo) defer |= jobs[j].cap >= al->defer && jobs[j].n >= al->defer_rows;
-        }
-        A.defer = defer ? al->defer : 0;
         A.defer_rows = al->defer_rows;
-        // deferred bad regions: of the long jobs (defer) and of every split job
-        const bool deferring = defer || !splits.empty();
-        if (deferring) {
-            al->d_job_regions.grow((size_t)n_reg);
-            al->d_job_nreg.grow(jobs.size());
-            al->d_fin.grow(jobs.size());
-            const int64_t max_sub = n_sub_max;
-            al->d_subs.grow((size_t)max_sub);
-            al->d_sub_res.grow((size_t)max_sub);
-            al->d_alloc.ensure(2);
-            al->d_counters.ensure(8);
-            // sub-job outputs: about what the jobs' own scratch holds
-            al->d_pool.grow((size_t)scratch + (16u << 20));
-            zero(al->d_alloc.p, 16);
-            zero(al->d_counters.p, 32);
-            A.job_regions = al->d_job_regions.p;
-            A.job_nreg = al->d_job_nreg.p;
-            A.subs = al->d_subs.p;
-            A.sub_res = al->d_sub_res.p;
-            A.alloc = al->d_alloc.p;
-            A.counters = al->d_counters.p;
-            A.pool = al->d_pool.p;
-            A.pool_cap = (int64_t)al->d_pool.cap;
-            A.max_sub = max_sub;
-            A.fin = al->d_fin.p;
-        } else {
-            A.job_regions = nullptr;
-            A.job_nreg = nullptr;
-            A.subs = nullptr;
-            A.sub_res = nullptr;
-            A.alloc = nullptr;
-            A.counters = nullptr;
-            A.pool = nullptr;
-            A.pool_cap = 0;
-            A.max_sub = 0;
-            A.fin = nullptr;
+        return A;
+    }
+
+    // the LDS plan (the async re-run carries the first attempt's)
+    void lds_args(SaArgs& A, const SaLds& l) {
+        A.stage_bytes = l.stage_bytes;
+        A.hist_cap = l.hist_cap;
+        A.words_bytes = l.words_bytes;
+        A.ltab_log2 = l.ltab_log2;
+    }
+
+    // deferred bad regions (of the long jobs, `defer`, and of every split job): their lists, the sub-jobs and the
+    // pool of the sub-jobs' outputs
+    void defer_args(SaArgs& A, bool defer, int64_t scratch) {
+        A.defer = defer ? al->defer : 0;
+        if (!defer && p.splits.empty()) return;
+        A.job_regions = al->d_job_regions.grow((size_t)p.n_reg);
+        A.job_nreg = al->d_job_nreg.grow(p.jobs.size());
+        A.fin = al->d_fin.grow(p.jobs.size());
+        A.subs = al->d_subs.grow((size_t)p.n_sub_max);
+        A.sub_res = al->d_sub_res.grow((size_t)p.n_sub_max);
+        A.max_sub = p.n_sub_max;
+        A.alloc = al->d_alloc.ensure(2);
+        A.counters = al->d_counters.ensure(8);
+        zero(A.alloc, 16);
+        zero(A.counters, 32);
+        // sub-job outputs: about what the jobs' own scratch holds
+        A.pool = al->d_pool.grow((size_t)scratch + (16u << 20));
+        A.pool_cap = (int64_t)al->d_pool.cap;
+    }
+
+    // unsplit twins: their offsets, states and output pool
+    void twin_args(SaArgs& A) {
+        if (!p.n_utw) return;
+        const size_t n = (size_t)n_jobs;
+        A.utw_pool = al->d_utw_pool.grow((size_t)std::max<int64_t>(p.utw_bytes, 256));
+        A.utw_off = al->d_utw_off.grow(n);
+        A.utw_state = al->d_utw_st.grow(2 * n);
+        A.utw_len = A.utw_state + n;
+        put(al->d_utw_off.p, p.utw_off.data(), n * 8);
+        zero(A.utw_state, 2 * n * 4);
+    }
+
+    // split jobs (the host plan) and room for the sub-job splits (k_plan_subs, when bad regions are deferred and
+    // the split length is not 0): the segment length, the work areas and chains of the job splits, the split state
+    void split_args(SaArgs& A, bool deferring, bool split_subs, int64_t scratch) {
+        A.split_len = al->opt.aligner_type == 0 ? al->split : 0;
+        if (p.post_bytes > 0) A.post_area = al->d_post.grow((size_t)p.post_bytes);
+        if (!p.splits.empty()) {
+            A.chain = al->d_chain.grow(p.segs.size());
+            A.chain_hdr = al->d_chain_hdr.grow(p.splits.size());
+            A.chain_bits = al->d_chain_bits.grow((size_t)std::max<int64_t>(p.bits_words, 1));
+            A.bits_off = al->d_bits_off.grow(p.bits_off.size());
+            A.part0 = al->d_part0.grow(p.part0.size());
+            put(al->d_bits_off.p, p.bits_off.data(), p.bits_off.size() * 8);
+            put(al->d_part0.p, p.part0.data(), p.part0.size() * 4);
         }
-        pmark(5);
-        // LDS: word table (20 B/entry) + the largest job's rows.  A workgroup may
-        // take all 160 KiB of a CU's LDS; when the batch has more jobs than
-        // workgroups can be resident at that size the stage shrinks, and the
-        // jobs that no longer fit read their rows from global memory.
-        // LDS per workgroup: the 64-shift chunk words (vector search, up to
-        // VEC_ROWS rows), the word table of the row-parallel search (more rows:
-        // up to half of what is left) and the stage for the job's rows.  The
-        // budget shrinks as more workgroups must be resident per CU.
-        int64_t max_rows = 0;
-        for (int32_t j : todo) max_rows = std::max<int64_t>(max_rows, jsum[j]);
-        const int64_t per_cu = std::min<int64_t>(4 * wv, std::max<int64_t>(1, ((int64_t)nj + 255) / 256));
-        const int64_t budget = LDS_PER_CU / per_cu;
-        // word history of the row-parallel search (HIST_SHIFTS x 64 words) when
-        // the budget allows
-        const int64_t hist_bytes = 64 * HIST_SHIFTS * 8;
-        A.hist_cap = (max_n > VEC_ROWS && hist_bytes * 4 <= budget) ? HIST_SHIFTS : 0;
-        const int64_t words_bytes = std::max<int64_t>(64 * VEC_ROWS * 8, A.hist_cap ? hist_bytes : 0);
-        A.words_bytes = (int32_t)words_bytes;
-        A.ltab_log2 = 0;
-        if (max_n > VEC_ROWS)
-            while (A.ltab_log2 < 12 && (20ll << (A.ltab_log2 + 1)) <= (budget - words_bytes) / 2) A.ltab_log2++;
-        // key, row mask and completion shift per entry
-        const int64_t ltab = 1ll << A.ltab_log2;
-        const int table_bytes = (int)(16 * ltab + 8 * ((ltab + 1) / 2) + words_bytes);
-        const int64_t stage_cap = std::max<int64_t>(0, budget - table_bytes);
-        // short jobs keep A|B|C in the stage too (k_align_jobs): size the stage
-        // for the largest such job within the budget
-        int64_t max_need = (max_rows + 15) & ~15ll;
-        for (int32_t j : todo) {
-            if (A.defer != 0 && jobs[j].cap >= A.defer && jobs[j].n >= A.defer_rows) continue;
-            const int64_t need = (((int64_t)jsum[j] + 15) & ~15ll) + 3ll * jobs[j].n * jobs[j].cap;
-            if (need <= stage_cap) max_need = std::max(max_need, need);
+        if (p.splits.empty() && !split_subs) return;
+        const size_t subs = (size_t)std::max<int64_t>(1, p.n_sub_max);
+        A.cap_splits = (int32_t)p.splits.size() + (split_subs ? (int32_t)std::min<int64_t>(p.n_sub_max, 1 << 20) : 0);
+        A.cap_segs = (int32_t)p.segs.size() + (split_subs ? (1 << 17) : 0);
+        A.cap_tgt = p.n_tgt + (split_subs ? (1ll << 22) : 0);
+        A.cap_find = (int64_t)p.ftasks.size() + (split_subs ? (1ll << 17) : 0);
+        A.cap_pool = p.seg_bytes + (split_subs ? std::max<int64_t>(256ll << 20, 4 * (scratch + (16 << 20))) : 0);
+        const size_t cap_segs = (size_t)std::max(1, A.cap_segs);
+        A.splits = al->d_splits.grow((size_t)std::max(1, A.cap_splits));
+        A.segs = al->d_segs.grow(cap_segs);
+        A.ftasks = al->d_ftasks.grow((size_t)std::max<int64_t>(1, A.cap_find));
+        A.targets = al->d_targets.grow((size_t)std::max<int64_t>(1, A.cap_tgt));
+        A.seg_res = al->d_seg_res.grow(cap_segs);
+        A.seg_wall = al->d_seg_wall.grow(2 * cap_segs);
+        A.seg_pool = al->d_seg_pool.grow((size_t)std::max<int64_t>(256, A.cap_pool));
+        A.qseg = al->d_qseg.grow(cap_segs);
+        A.qsub = al->d_qsub.grow(subs);
+        A.sctr = al->d_sctr.ensure(SC_N);
+        if (!p.splits.empty()) {
+            put(al->d_splits.p, p.splits.data(), p.splits.size() * sizeof(SaSplit));
+            put(al->d_segs.p, p.segs.data(), p.segs.size() * sizeof(SaSeg));
+            put(al->d_ftasks.p, p.ftasks.data(), p.ftasks.size() * sizeof(int2));
         }
-        A.stage_bytes = o.aligner_type == 0 ? (int32_t)std::min<int64_t>(max_need, stage_cap & ~15ll) : 0;
-        const size_t lds_bytes = (size_t)table_bytes + (size_t)A.stage_bytes;
-        NPGX_REQUIRE(A.stage_bytes >= 0 && lds_bytes <= (size_t)LDS_PER_CU, NPGX_ERR_STATE, "LDS budget");
-        A.splits = nullptr;
-        A.segs = nullptr;
-        A.targets = nullptr;
-        A.seg_res = nullptr;
-        A.seg_wall = nullptr;
-        A.sub_wall = nullptr;
-        A.seg_pool = nullptr;
-        A.sctr = nullptr;
-        A.qseg = nullptr;
-        A.qsub = nullptr;
-        A.rq = nullptr;
-        A.out = as ? as->out : nullptr;
-        A.err = as ? as->err : nullptr;
-        A.retried = as ? al->d_retried.p : nullptr;
-        A.order1 = as ? al->d_order1.p : nullptr;
-        A.ctr1 = as ? al->d_ctr1.p : nullptr;
-        A.ftasks = nullptr;
-        A.split_len = o.aligner_type == 0 ? al->split : 0;
-        A.utw_off = nullptr;
-        A.utw_state = nullptr;
-        A.utw_len = nullptr;
-        A.utw_pool = nullptr;
-        if (n_utw) {
-            al->d_utw_pool.grow((size_t)std::max<int64_t>(utw_bytes, 256));
-            al->d_utw_off.grow((size_t)n_jobs);
-            al->d_utw_st.grow(2 * (size_t)n_jobs);
-            put(al->d_utw_off.p, uoff.data(), (size_t)n_jobs * 8);
-            zero(al->d_utw_st.p, 2 * (size_t)n_jobs * 4);
-            A.utw_off = al->d_utw_off.p;
-            A.utw_state = al->d_utw_st.p;
-            A.utw_len = al->d_utw_st.p + n_jobs;
-            A.utw_pool = al->d_utw_pool.p;
+        const uint32_t sc[SC_N] = {(uint32_t)p.splits.size(), (uint32_t)p.segs.size(), (uint32_t)p.n_tgt,
+                                   (uint32_t)p.ftasks.size(), 0u, 0u, (uint32_t)p.seg_bytes,
+                                   (uint32_t)((uint64_t)p.seg_bytes >> 32)};
+        put(A.sctr, sc, sizeof(sc));
+        if (al->want_stats && deferring) {
+            A.sub_wall = al->d_sub_wall.grow(2 * subs);
+            NPGX_HIP(hipMemsetAsync(A.sub_wall, 0, 2 * subs * 8, st));
         }
-        A.post_area = nullptr;
-        if (post_bytes > 0) {
-            al->d_post.grow((size_t)post_bytes);
-            A.post_area = al->d_post.p;
-        }
-        A.chain = nullptr;
-        A.chain_hdr = nullptr;
-        A.chain_bits = nullptr;
-        A.bits_off = nullptr;
-        A.part0 = nullptr;
-        if (!splits.empty()) {
-            al->d_chain.grow(segs.size());
-            al->d_chain_hdr.grow(splits.size());
-            al->d_chain_bits.grow((size_t)std::max<int64_t>(bits_words, 1));
-            al->d_bits_off.grow(bits_off.size());
-            al->d_part0.grow(part0.size());
-            put(al->d_bits_off.p, bits_off.data(), bits_off.size() * 8);
-            put(al->d_part0.p, part0.data(), part0.size() * 4);
-            A.chain = al->d_chain.p;
-            A.chain_hdr = al->d_chain_hdr.p;
-            A.chain_bits = al->d_chain_bits.p;
-            A.bits_off = al->d_bits_off.p;
-            A.part0 = al->d_part0.p;
-        }
-        A.cap_splits = A.cap_segs = 0;
-        A.cap_tgt = A.cap_find = A.cap_pool = 0;
-        const int n_job_splits = (int)splits.size(), n_job_find = (int)ftasks.size();
-        const bool split_subs = deferring && A.split_len > 0;
-        if (!splits.empty() || split_subs) {
-            // the job splits (host plan) and room for the sub-job splits (k_plan_subs)
-            A.cap_splits = n_job_splits + (split_subs ? (int32_t)std::min<int64_t>(n_sub_max, 1 << 20) : 0);
-            A.cap_segs = (int32_t)segs.size() + (split_subs ? (1 << 17) : 0);
-            A.cap_tgt = n_tgt + (split_subs ? (1ll << 22) : 0);
-            A.cap_find = n_job_find + (split_subs ? (1ll << 17) : 0);
-            A.cap_pool = seg_bytes + (split_subs ? std::max<int64_t>(256ll << 20, 4 * (int64_t)(scratch + (16 << 20))) : 0);
-            al->d_splits.grow((size_t)std::max(1, A.cap_splits));
-            al->d_segs.grow((size_t)std::max(1, A.cap_segs));
-            al->d_ftasks.grow((size_t)std::max<int64_t>(1, A.cap_find));
-            al->d_targets.grow((size_t)std::max<int64_t>(1, A.cap_tgt));
-            al->d_seg_res.grow((size_t)std::max(1, A.cap_segs));
-            al->d_seg_wall.grow(2 * (size_t)std::max(1, A.cap_segs));
-            al->d_seg_pool.grow((size_t)std::max<int64_t>(256, A.cap_pool));
-            al->d_qseg.grow((size_t)std::max(1, A.cap_segs));
-            al->d_qsub.grow((size_t)std::max<int64_t>(1, n_sub_max));
-            al->d_sctr.ensure(SC_N);
-            if (!splits.empty()) {
-                put(al->d_splits.p, splits.data(), splits.size() * sizeof(SaSplit));
-                put(al->d_segs.p, segs.data(), segs.size() * sizeof(SaSeg));
-                put(al->d_ftasks.p, ftasks.data(), ftasks.size() * sizeof(int2));
-            }
-            const uint32_t sc[SC_N] = {(uint32_t)n_job_splits, (uint32_t)segs.size(), (uint32_t)n_tgt,
-                                       (uint32_t)n_job_find, 0u, 0u, (uint32_t)seg_bytes,
-                                       (uint32_t)((uint64_t)seg_bytes >> 32)};
-            put(al->d_sctr.p, sc, sizeof(sc));
-            A.splits = al->d_splits.p;
-            A.segs = al->d_segs.p;
-            A.targets = al->d_targets.p;
-            A.seg_res = al->d_seg_res.p;
-            A.seg_wall = al->d_seg_wall.p;
-            if (al->want_stats && deferring) {
-                al->d_sub_wall.grow(2 * (size_t)std::max<int64_t>(1, n_sub_max));
-                NPGX_HIP(hipMemsetAsync(al->d_sub_wall.p, 0, 2 * (size_t)std::max<int64_t>(1, n_sub_max) * 8, st));
-                A.sub_wall = al->d_sub_wall.p;
-            }
-            A.seg_pool = al->d_seg_pool.p;
-            A.sctr = al->d_sctr.p;
-            A.qseg = al->d_qseg.p;
-            A.qsub = al->d_qsub.p;
-            A.ftasks = al->d_ftasks.p;
+    }
+
+    // async mode: where the finishing waves write the results and list the re-run
+    void async_args(SaArgs& A) {
+        if (!as) return;
+        A.out = as->out;
+        A.err = as->err;
+        A.retried = al->d_retried.p;
+        A.order1 = al->d_order1.p;
+        A.ctr1 = al->d_ctr1.p;
+    }
+
+    // An attempt over p.queue up to its k_align_jobs launch: uploads, slots, LDS plan, arguments, the job splits'
+    // sync states (align_split), the jobs
+    SaLaunch enqueue_jobs(const SaAttempt& at, const SaSlots* async_rerun) {
+        SaLaunch L;
+        L.b = at.b;
+        const int nj = (int)p.queue.size();
+        at.scr->grow((size_t)std::max<int64_t>(at.b.scratch, 256));  // (1.5x headroom: batches grow loop by loop)
+        put(al->d_jobs.p, p.jobs.data(), p.jobs.size() * sizeof(SaJob));
+        al->d_order.grow(p.queue.size());
+        put(al->d_order.p, p.queue.data(), p.queue.size() * 4);
+        zero(al->d_next.p, 4);
+        clk.mark(3);
+        int64_t cols_need = 256;
+        for (int32_t q : p.queue)
+            if (q >= 0 && q < UTWIN_BASE) cols_need = std::max<int64_t>(cols_need, (int64_t)p.jobs[q].cap + 1);
+        L.wv = nj > SA_WAVES_MANY_AT ? SA_WAVES_MANY : SA_WAVES_PER_EU;
+        // wv waves on each of the 4 SIMDs of the 256 CUs
+        L.s = size_slots(at.b, cols_need, std::min(nj, 256 * 4 * L.wv), at.first);
+        grow_slot_buffers(L.s, async_rerun);
+        clk.mark(4);
+        L.defer = false;  // (true: some job long enough and with enough rows)
+        if (at.first && al->defer > 0 && al->opt.aligner_type == 0 && p.n_reg > 0 && at.b.max_cap >= al->defer)
+            for (int32_t j : p.todo) L.defer |= p.jobs[j].cap >= al->defer && p.jobs[j].n >= al->defer_rows;
+        L.deferring = L.defer || !p.splits.empty();
+        L.split_subs = L.deferring && al->opt.aligner_type == 0 && al->split > 0;
+        L.A = base_args(al->d_jobs.p, al->d_order.p, nj, al->d_next.p, at.scr->p, L.s);
+        defer_args(L.A, L.defer, at.b.scratch);
+        clk.mark(5);
+        L.lds = plan_lds(at.b, nj, L.wv, L.A.defer);
+        lds_args(L.A, L.lds);
+        twin_args(L.A);
+        split_args(L.A, L.deferring, L.split_subs, at.b.scratch);
+        async_args(L.A);
+        const int n_job_find = (int)p.ftasks.size();
+        if (!p.splits.empty() || L.split_subs) {
             flush();
-            if (n_job_find > 0) {
-                size_t tf = al->timer.begin("align_split", st, 0.0, (int64_t)n_job_find);
-                hipLaunchKernelGGL(k_split_find, dim3((unsigned)n_job_find), dim3(64 * SPLIT_WAVES), SPLIT_LDS, st, A,
-                                   al->d_ftasks.p, n_job_find, 0);
-                NPGX_HIP(hipGetLastError());
-                al->timer.end(tf, st);
-            }
+            if (n_job_find > 0)
+                timed("align_split", 0.0, (int64_t)n_job_find, [&] {
+                    hipLaunchKernelGGL(k_split_find, dim3((unsigned)n_job_find), dim3(64 * SPLIT_WAVES), SPLIT_LDS, st,
+                                       L.A, al->d_ftasks.p, n_job_find, 0);
+                });
         }
-        pmark(6);
+        clk.mark(6);
         int64_t residues = 0;
-        for (int32_t j : todo) residues += jsum[j];
+        for (int32_t j : p.todo) residues += p.jsum[j];
         if (as) {
-            put(al->d_jobs1.p, al->h_jobs1.data(), al->h_jobs1.size() * sizeof(SaJob));
+            put(al->d_jobs1.p, p.jobs1.data(), p.jobs1.size() * sizeof(SaJob));
             zero(al->d_ctr1.p, 8);
-            zero(al->d_retried.p, jobs.size());
+            zero(al->d_retried.p, p.jobs.size());
         }
         flush();
-        size_t ti = al->timer.begin(attempt == 0 ? "align_jobs" : "align_jobs_retry", st,
-                                    double(residues) * 2.0, residues);
-        launch_sa(k_align_jobs<true, SA_WAVES_PER_EU>, k_align_jobs<false, SA_WAVES_PER_EU>,
-                  k_align_jobs<true, SA_WAVES_MANY>, k_align_jobs<false, SA_WAVES_MANY>, wv, slots, lds_bytes, A);
-        NPGX_HIP(hipGetLastError());
-        al->timer.end(ti, st);
-        pmark(7);
-        if (!splits.empty()) {  // the split jobs: chain, regions, deferred bad regions
-            ti = al->timer.begin("align_split_chain", st, 0.0, (int64_t)n_job_splits);
-            hipLaunchKernelGGL(k_split_chain, dim3((unsigned)n_job_splits), dim3(POST_THREADS), 0, st, A);
-            NPGX_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_chain_copy, dim3((unsigned)part0.back()), dim3(POST_THREADS), 0, st, A,
-                               n_job_splits);
-            NPGX_HIP(hipGetLastError());
-            al->timer.end(ti, st);
-            ti = al->timer.begin("align_split_post", st, 0.0, (int64_t)n_job_splits);
-            hipLaunchKernelGGL(k_split_post, dim3((unsigned)n_job_splits), dim3(REG_THREADS), POST_LDS, st, A,
-                               (int)POST_LDS);
-            NPGX_HIP(hipGetLastError());
-            al->timer.end(ti, st);
-        }
-        if (deferring) {  // the deferred bad regions, then their jobs (no-ops when nothing was deferred)
-            // jobs that may have deferred: the split ones and the long ones
-            int64_t n_fin = (int64_t)n_job_splits;
-            int64_t max_rc = 1;
-            {
-                std::vector<uint8_t> is_split(n_jobs, 0);
-                for (const SaSplit& sp : splits) is_split[sp.job] = 1;
-                for (int32_t j : todo) {
-                    const bool may = is_split[j] || (defer && jobs[j].cap >= al->defer && jobs[j].n >= al->defer_rows);
-                    if (!may) continue;
-                    n_fin += is_split[j] ? 0 : 1;
-                    max_rc = std::max<int64_t>(max_rc, jobs[j].reg_cap + 1);
-                }
-            }
-            const int lds_ints = (int)std::min<int64_t>(max_rc, 32768);
-            al->d_reg_dst.grow((size_t)n_reg + jobs.size());
-            if (!splits.empty()) {  // the rows of the split jobs' bad regions
-                ti = al->timer.begin("align_sub_rows", st, 0.0, 0);
-                hipLaunchKernelGGL(k_sub_rows, dim3(1024), dim3(256), 0, st, A, max_n);
+        timed(at.name, double(residues) * 2.0, residues, [&] { launch_sa<JobsK>(L.wv, L.s.n, L.lds.lds_bytes, L.A); });
+        clk.mark(7);
+        return L;
+    }
+
+    // After the jobs: the split jobs' chains and regions, then the deferred bad regions as sub-jobs and their jobs'
+    // B (no-ops when nothing was deferred)
+    void enqueue_deferred(const SaLaunch& L) {
+        if (!L.deferring) return;
+        const SaArgs& A = L.A;
+        const int n_job_splits = (int)p.splits.size(), n_job_find = (int)p.ftasks.size();
+        if (n_job_splits) {
+            timed("align_split_chain", 0.0, (int64_t)n_job_splits, [&] {
+                hipLaunchKernelGGL(k_split_chain, dim3((unsigned)n_job_splits), dim3(POST_THREADS), 0, st, A);
                 NPGX_HIP(hipGetLastError());
-                al->timer.end(ti, st);
-            }
-            if (split_subs) {  // the long sub-jobs: plan, sync states
-                ti = al->timer.begin("align_sub_split", st, 0.0, 0);
+                hipLaunchKernelGGL(k_chain_copy, dim3((unsigned)p.part0.back()), dim3(POST_THREADS), 0, st, A,
+                                   n_job_splits);
+            });
+            timed("align_split_post", 0.0, (int64_t)n_job_splits, [&] {
+                hipLaunchKernelGGL(k_split_post, dim3((unsigned)n_job_splits), dim3(REG_THREADS), POST_LDS, st, A,
+                                   (int)POST_LDS);
+            });
+        }
+        // jobs that may have deferred: the split ones and the long ones
+        int64_t n_fin = (int64_t)n_job_splits;
+        int64_t max_rc = 1;
+        for (int32_t j : p.todo) {
+            const bool may = p.is_split[j] || (L.defer && p.jobs[j].cap >= al->defer && p.jobs[j].n >= al->defer_rows);
+            if (!may) continue;
+            n_fin += p.is_split[j] ? 0 : 1;
+            max_rc = std::max<int64_t>(max_rc, p.jobs[j].reg_cap + 1);
+        }
+        const int lds_ints = (int)std::min<int64_t>(max_rc, 32768);
+        al->d_reg_dst.grow((size_t)p.n_reg + p.jobs.size());
+        if (n_job_splits)  // the rows of the split jobs' bad regions
+            timed("align_sub_rows", 0.0, 0,
+                  [&] { hipLaunchKernelGGL(k_sub_rows, dim3(1024), dim3(256), 0, st, A, L.b.max_n); });
+        if (L.split_subs)  // the long sub-jobs: plan, sync states
+            timed("align_sub_split", 0.0, 0, [&] {
                 hipLaunchKernelGGL(k_plan_subs, dim3(256), dim3(256), 0, st, A);
                 NPGX_HIP(hipGetLastError());
-                hipLaunchKernelGGL(k_split_find, dim3(2048), dim3(64 * SPLIT_WAVES), SPLIT_LDS, st, A, al->d_ftasks.p, -1,
-                                   n_job_find);
-                NPGX_HIP(hipGetLastError());
-                al->timer.end(ti, st);
-            }
-            ti = al->timer.begin("align_sub", st, 0.0, 0);
-            launch_sa(k_align_sub<true, SA_WAVES_PER_EU>, k_align_sub<false, SA_WAVES_PER_EU>,
-                      k_align_sub<true, SA_WAVES_MANY>, k_align_sub<false, SA_WAVES_MANY>, wv, slots, lds_bytes, A);
-            NPGX_HIP(hipGetLastError());
-            al->timer.end(ti, st);
-            if (split_subs) {  // the split sub-jobs' chains
-                ti = al->timer.begin("align_sub_post", st, 0.0, 0);
-                hipLaunchKernelGGL(k_sub_post, dim3(512), dim3(POST_THREADS), 0, st, A, n_job_splits);
-                NPGX_HIP(hipGetLastError());
-                al->timer.end(ti, st);
-                // the failed sub-jobs again, whole, at their proven bound (one
-                // launch, usually empty): a split sub-job whose chain broke or
-                // overflowed no longer sends its job to attempt 1 whole
-                // 
-                al->d_rq.grow((size_t)std::max<int64_t>(n_sub_max, 1));
-                SaArgs A2 = A;
-                A2.rq = al->d_rq.p;
-                ti = al->timer.begin("align_sub_retry", st, 0.0, 0);
+                hipLaunchKernelGGL(k_split_find, dim3(2048), dim3(64 * SPLIT_WAVES), SPLIT_LDS, st, A, al->d_ftasks.p,
+                                   -1, n_job_find);
+            });
+        timed("align_sub", 0.0, 0, [&] { launch_sa<SubK>(L.wv, L.s.n, L.lds.lds_bytes, A); });
+        if (L.split_subs) {  // the split sub-jobs' chains
+            timed("align_sub_post", 0.0, 0,
+                  [&] { hipLaunchKernelGGL(k_sub_post, dim3(512), dim3(POST_THREADS), 0, st, A, n_job_splits); });
+            // the failed sub-jobs again, whole, at their proven bound (one launch,
+            // usually empty): a split sub-job whose chain broke or overflowed no
+            // longer sends its job to the re-run whole
+            al->d_rq.grow((size_t)std::max<int64_t>(p.n_sub_max, 1));
+            SaArgs A2 = A;
+            A2.rq = al->d_rq.p;
+            timed("align_sub_retry", 0.0, 0, [&] {
                 hipLaunchKernelGGL(k_sub_retry_list, dim3(256), dim3(256), 0, st, A2);
-                launch_sa(k_align_sub<true, SA_WAVES_PER_EU>, k_align_sub<false, SA_WAVES_PER_EU>,
-                          k_align_sub<true, SA_WAVES_MANY>, k_align_sub<false, SA_WAVES_MANY>, wv, slots, lds_bytes, A2);
-                NPGX_HIP(hipGetLastError());
-                al->timer.end(ti, st);
-            }
-            if (n_fin > 0) {
-                ti = al->timer.begin("align_fin_copy", st, 0.0, 0);
+                launch_sa<SubK>(L.wv, L.s.n, L.lds.lds_bytes, A2);
+            });
+        }
+        if (n_fin > 0)
+            timed("align_fin_copy", 0.0, 0, [&] {
                 hipLaunchKernelGGL(k_fin_prefix, dim3((unsigned)n_fin), dim3(REG_THREADS), 0, st, A, al->d_reg_dst.p);
                 NPGX_HIP(hipGetLastError());
                 hipLaunchKernelGGL(k_fin_copy, dim3((unsigned)(n_fin * FIN_PARTS)), dim3(POST_THREADS),
                                    (size_t)lds_ints * 4, st, A, lds_ints, al->d_reg_dst.p);
-                NPGX_HIP(hipGetLastError());
-                al->timer.end(ti, st);
-            }
-            ti = al->timer.begin("align_finish", st, 0.0, 0);
-            if (al->long_head > 0) hipLaunchKernelGGL(k_align_finish<true>, dim3((unsigned)slots), dim3(64), lds_bytes, st, A);
-            else hipLaunchKernelGGL(k_align_finish<false>, dim3((unsigned)slots), dim3(64), lds_bytes, st, A);
-            NPGX_HIP(hipGetLastError());
-            al->timer.end(ti, st);
-        }
-        if (!splits.empty() && getenv("NPGX_SPLIT_DEBUG")) {  // diagnostic: sync states and segment results
-            std::vector<int32_t> tg((size_t)n_tgt);
-            std::vector<int4> sr(segs.size());
-            NPGX_HIP(hipMemcpyAsync(tg.data(), al->d_targets.p, tg.size() * 4, hipMemcpyDeviceToHost, st));
-            NPGX_HIP(hipMemcpyAsync(sr.data(), al->d_seg_res.p, sr.size() * 16, hipMemcpyDeviceToHost, st));
-            NPGX_HIP(hipStreamSynchronize(st));
-            for (const SaSplit& sp : splits) {
-                const int n = jobs[sp.job].n;
-                int valid = 0, ovf = 0, hits = 0;
-                for (int k = 1; k < sp.K; k++) valid += tg[sp.tgt + (int64_t)(k - 1) * n] >= 0;
-                std::string chain;
-                for (int k = 0; k < sp.K; k++) {
-                    const int4 r = sr[sp.seg0 + k];
-                    ovf += r.z;
-                    hits += r.x >= 0 && r.x < sp.K;
-                }
-                for (int k = 0, guard = 0; k < sp.K && k >= 0 && guard < 1000; guard++) {
-                    const int4 r = sr[sp.seg0 + k];
-                    chain += std::to_string(k) + "(" + std::to_string(r.y) + (r.z ? "!" : "") + ")>";
-                    if (r.x <= k) break;
-                    k = r.x;
-                }
-                fprintf(stderr, "split job %d n=%d K=%d maxlen=%d valid_states=%d hits=%d ovf=%d chain %s\n", sp.job,
-                        n, sp.K, jmax[sp.job], valid, hits, ovf, chain.c_str());
-            }
-            // per job, when its own walk or its last segment ended in k_align_jobs
-            // (wall clock; the sub-job launch below sets its sub-jobs beside it)
-            std::vector<int64_t> walk_end;
-            int64_t crit_t0 = INT64_MAX;
-            if (al->want_stats) {  // the slowest segments (wall clock at 100 MHz)
-                std::vector<int64_t> sw(2 * segs.size());
-                NPGX_HIP(hipMemcpy(sw.data(), al->d_seg_wall.p, sw.size() * 8, hipMemcpyDeviceToHost));
-                std::vector<std::pair<int64_t, int>> d;
-                for (size_t q = 0; q < segs.size(); q++) d.push_back({sw[2 * q + 1] - sw[2 * q], (int)q});
-                std::sort(d.rbegin(), d.rend());
-                for (size_t q = 0; q < std::min<size_t>(5, d.size()); q++) {
-                    const int4 r = sr[(size_t)d[q].second];
-                    fprintf(stderr, "slow segment %d: %.1f us, %d cols, next %d (K %d), n %d\n", d[q].second,
-                            d[q].first / 100.0, r.y, r.x, splits[segs[(size_t)d[q].second].split].K,
-                            jobs[splits[segs[(size_t)d[q].second].split].job].n);
-                }
-                // the launch's critical path: when the segments and the whole jobs end
-                std::vector<int64_t> js((size_t)n_jobs * NPGX_JOB_STATS);
-                NPGX_HIP(hipMemcpy(js.data(), al->d_job_stats.p, js.size() * 8, hipMemcpyDeviceToHost));
-                int64_t t0 = INT64_MAX, se = 0, je = 0, jd = 0;
-                int jslow = -1;
-                walk_end.assign(n_jobs, 0);
-                for (size_t q = 0; q < segs.size(); q++) {
-                    t0 = std::min(t0, sw[2 * q]);
-                    se = std::max(se, sw[2 * q + 1]);
-                    int64_t& we = walk_end[splits[segs[q].split].job];
-                    we = std::max(we, sw[2 * q + 1]);
-                }
-                std::vector<uint8_t> was_split(n_jobs, 0);
-                for (const SaSplit& sp2 : splits) was_split[sp2.job] = 1;
-                for (int32_t j : todo) {
-                    const int64_t* r = js.data() + (size_t)j * NPGX_JOB_STATS;
-                    if (was_split[j] || r[11] <= 0 || r[23] <= 0) continue;
-                    t0 = std::min(t0, r[11]);
-                    je = std::max(je, r[23]);
-                    walk_end[j] = r[23];
-                    if (r[23] - r[11] > jd) {
-                        jd = r[23] - r[11];
-                        jslow = j;
-                    }
-                }
-                if (t0 != INT64_MAX)
-                    fprintf(stderr, "launch: segments end at %.1f us, whole jobs at %.1f us; slowest whole job %d: "
-                            "%.1f us, %lld cols, %d rows (process_seqs %.1f us, regions+realign %.1f us)\n",
-                            (se - t0) / 100.0, (je - t0) / 100.0, jslow, jd / 100.0,
-                            jslow >= 0 ? (long long)js[(size_t)jslow * NPGX_JOB_STATS + 1] : 0ll,
-                            jslow >= 0 ? jobs[jslow].n : 0,
-                            jslow >= 0 ? js[(size_t)jslow * NPGX_JOB_STATS + 8] / 2400.0 : 0.0,
-                            jslow >= 0 ? js[(size_t)jslow * NPGX_JOB_STATS + 9] / 2400.0 : 0.0);
-                crit_t0 = t0;
-            }
-            if (deferring) {  // sub-jobs: count and widths
-                unsigned long long al2[2];
-                NPGX_HIP(hipMemcpy(al2, al->d_alloc.p, 16, hipMemcpyDeviceToHost));
-                std::vector<SaSub> sb((size_t)al2[1]);
-                std::vector<int2> rs((size_t)al2[1]);
-                if (!sb.empty()) {
-                    NPGX_HIP(hipMemcpy(sb.data(), al->d_subs.p, sb.size() * sizeof(SaSub), hipMemcpyDeviceToHost));
-                    NPGX_HIP(hipMemcpy(rs.data(), al->d_sub_res.p, rs.size() * 8, hipMemcpyDeviceToHost));
-                }
-                if (al->want_stats && A.sub_wall && !sb.empty()) {  // the sub-job launch's critical path
-                    std::vector<int64_t> sw2(2 * sb.size());
-                    NPGX_HIP(hipMemcpy(sw2.data(), al->d_sub_wall.p, sw2.size() * 8, hipMemcpyDeviceToHost));
-                    unsigned int sc2[SC_N];
-                    NPGX_HIP(hipMemcpy(sc2, al->d_sctr.p, sizeof(sc2), hipMemcpyDeviceToHost));
-                    std::vector<int64_t> segw(2 * (size_t)std::max(1, A.cap_segs));
-                    NPGX_HIP(hipMemcpy(segw.data(), al->d_seg_wall.p, segw.size() * 8, hipMemcpyDeviceToHost));
-                    int64_t t0 = INT64_MAX, wend = 0, send = 0, wmax = 0;
-                    int wslow = -1;
-                    for (size_t q = 0; q < sb.size(); q++)
-                        if (sw2[2 * q] > 0) {
-                            t0 = std::min(t0, sw2[2 * q]);
-                            wend = std::max(wend, sw2[2 * q + 1]);
-                            if (sw2[2 * q + 1] - sw2[2 * q] > wmax) {
-                                wmax = sw2[2 * q + 1] - sw2[2 * q];
-                                wslow = (int)q;
-                            }
-                        }
-                    for (unsigned int q = (unsigned int)segs.size(); q < std::min(sc2[SC_SEGS], (unsigned)A.cap_segs); q++)
-                        if (segw[2 * q] > 0) {
-                            t0 = std::min(t0, segw[2 * q]);
-                            send = std::max(send, segw[2 * q + 1]);
-                        }
-                    // the pair's critical path by job: each job with sub-jobs, and
-                    // the job that ends either launch (tools/split_stats.py)
-                    if (crit_t0 != INT64_MAX && !walk_end.empty()) {
-                        const size_t nsg = std::min<size_t>(sc2[SC_SEGS], (size_t)A.cap_segs);
-                        const size_t nsp = std::min<size_t>(sc2[SC_SPLITS], (size_t)A.cap_splits);
-                        std::vector<SaSeg> dsg(nsg);
-                        std::vector<SaSplit> dsp(nsp);
-                        if (nsg) NPGX_HIP(hipMemcpy(dsg.data(), al->d_segs.p, nsg * sizeof(SaSeg), hipMemcpyDeviceToHost));
-                        if (nsp) NPGX_HIP(hipMemcpy(dsp.data(), al->d_splits.p, nsp * sizeof(SaSplit), hipMemcpyDeviceToHost));
-                        std::vector<int64_t> s_start(n_jobs, INT64_MAX), s_end(n_jobs, 0);
-                        std::vector<int> s_cnt(n_jobs, 0);
-                        for (size_t q = 0; q < sb.size(); q++) {
-                            const int32_t j = sb[q].job;
-                            if (j < 0 || j >= n_jobs) continue;
-                            s_cnt[j]++;
-                            if (sw2[2 * q] <= 0) continue;  // (split: its segments below)
-                            s_start[j] = std::min(s_start[j], sw2[2 * q]);
-                            s_end[j] = std::max(s_end[j], sw2[2 * q + 1]);
-                        }
-                        for (size_t q = segs.size(); q < nsg; q++) {
-                            if (segw[2 * q] <= 0 || dsg[q].split < 0 || (size_t)dsg[q].split >= nsp) continue;
-                            const int32_t sub = dsp[(size_t)dsg[q].split].sub;
-                            if (sub < 0 || (size_t)sub >= sb.size()) continue;
-                            const int32_t j = sb[(size_t)sub].job;
-                            if (j < 0 || j >= n_jobs) continue;
-                            s_start[j] = std::min(s_start[j], segw[2 * q]);
-                            s_end[j] = std::max(s_end[j], segw[2 * q + 1]);
-                        }
-                        int j_jobs = -1, j_subs = -1;
-                        for (int32_t j = 0; j < n_jobs; j++) {
-                            if (walk_end[j] > 0 && (j_jobs < 0 || walk_end[j] > walk_end[j_jobs])) j_jobs = j;
-                            if (s_end[j] > 0 && (j_subs < 0 || s_end[j] > s_end[j_subs])) j_subs = j;
-                        }
-                        for (int32_t j = 0; j < n_jobs; j++)
-                            if (s_end[j] > 0)
-                                fprintf(stderr, "crit job %d: %d rows, %d cols, walk or last segment ends %.1f us; %d "
-                                        "sub-jobs start %.1f us, end %.1f us\n", j, jobs[j].n, jmax[j],
-                                        (walk_end[j] - crit_t0) / 100.0, s_cnt[j], (s_start[j] - crit_t0) / 100.0,
-                                        (s_end[j] - crit_t0) / 100.0);
-                        if (j_jobs >= 0 && j_subs >= 0)
-                            fprintf(stderr, "crit launches: k_align_jobs ends with job %d at %.1f us, k_align_sub with job "
-                                    "%d at %.1f us (%s); job %d's own sub-jobs could have started at %.1f us, the "
-                                    "launch's first started at %.1f us\n", j_jobs, (walk_end[j_jobs] - crit_t0) / 100.0,
-                                    j_subs, (s_end[j_subs] - crit_t0) / 100.0,
-                                    j_jobs == j_subs ? "the same job" : "another job", j_subs,
-                                    (walk_end[j_subs] - crit_t0) / 100.0, (t0 - crit_t0) / 100.0);
-                    }
-                    if (t0 != INT64_MAX)
-                        fprintf(stderr, "sub launch: %u sub segments end at %.1f us, whole subs at %.1f us; slowest whole "
-                                "sub %d: %.1f us, %d cols, %d rows\n", sc2[SC_SEGS] - (unsigned)segs.size(),
-                                send ? (send - t0) / 100.0 : 0.0, (wend - t0) / 100.0, wslow, wmax / 100.0,
-                                wslow >= 0 ? rs[(size_t)wslow].x : 0, wslow >= 0 ? jobs[sb[(size_t)wslow].job].n : 0);
-                }
-                std::vector<int> wd;
-                for (const int2& r : rs) wd.push_back(r.x);
-                std::sort(wd.begin(), wd.end());
-                long long tot = 0;
-                for (int x : wd) tot += x;
-                fprintf(stderr, "subs %zu total_cols %lld p50 %d p90 %d p99 %d max %d\n", wd.size(), tot,
-                        wd.empty() ? 0 : wd[wd.size() / 2], wd.empty() ? 0 : wd[wd.size() * 9 / 10],
-                        wd.empty() ? 0 : wd[wd.size() * 99 / 100], wd.empty() ? 0 : wd.back());
-            }
-        }
-        pmark(8);
-        if (as) {
-            // the overflowed jobs again at the proven bound (no splits, no
-            // deferred regions: attempt 1 of the synchronous path); the waves
-            // that finished the jobs have listed them and written every other
-            // job's rows (job_final), and the re-run's write its own
-            SaArgs A1 = A;
-            A1.jobs = al->d_jobs1.p;
-            A1.order = al->d_order1.p;
-            A1.n_jobs = 0;
-            A1.n_jobs_dev = al->d_ctr1.p;
-            A1.next_job = (unsigned int*)(al->d_ctr1.p + 1);
-            A1.scratch = al->d_scratch2.p;
-            A1.tcap_log2 = tlog1;
-            A1.st_depth_max = depth1;
-            A1.slot_cols = cols1;
-            A1.defer = 0;
-            A1.job_regions = nullptr;
-            A1.job_nreg = nullptr;
-            A1.subs = nullptr;
-            A1.sub_res = nullptr;
-            A1.alloc = nullptr;
-            A1.counters = nullptr;
-            A1.pool = nullptr;
-            A1.pool_cap = 0;
-            A1.max_sub = 0;
-            A1.fin = nullptr;
-            A1.splits = nullptr;
-            A1.segs = nullptr;
-            A1.targets = nullptr;
-            A1.seg_res = nullptr;
-            A1.seg_wall = nullptr;
-            A1.sub_wall = nullptr;
-            A1.seg_pool = nullptr;
-            A1.sctr = nullptr;
-            A1.qseg = nullptr;
-            A1.qsub = nullptr;
-            A1.ftasks = nullptr;
-            A1.post_area = nullptr;
-            A1.chain = nullptr;
-            A1.chain_hdr = nullptr;
-            A1.chain_bits = nullptr;
-            A1.bits_off = nullptr;
-            A1.part0 = nullptr;
-            A1.split_len = 0;
-            A1.utw_off = nullptr;
-            A1.utw_state = nullptr;
-            A1.utw_len = nullptr;
-            A1.utw_pool = nullptr;
-            A1.cap_splits = A1.cap_segs = 0;
-            A1.cap_tgt = A1.cap_find = A1.cap_pool = 0;
-            size_t tr = al->timer.begin("align_jobs_retry", st, 0.0, 0);
-            if (al->long_head > 0)
-                hipLaunchKernelGGL((k_align_jobs<true, SA_WAVES_PER_EU>), dim3((unsigned)slots1), dim3(64), lds_bytes, st, A1);
-            else
-                hipLaunchKernelGGL((k_align_jobs<false, SA_WAVES_PER_EU>), dim3((unsigned)slots1), dim3(64), lds_bytes, st, A1);
-            al->timer.end(tr, st);
-            NPGX_HIP(hipGetLastError());
-            NPGX_HIP(hipMemcpyAsync(as->epoch, d_slot_epoch, 4, hipMemcpyDeviceToDevice, st));
-            res.len.clear();
-            res.cap.clear();
-            res.bptr.clear();
-            al->host_ms[0] += ms(tp);
-            pmark(8);
-            if (pdbg)
-                fprintf(stderr, "align_device async %d jobs: prep %.3f order %.3f puts %.3f split_plan %.3f slots %.3f "
-                        "args %.3f lds+split %.3f launch %.3f post %.3f ms\n", n_jobs, pt[0], pt[1], pt[2], pt[3],
-                        pt[4], pt[5], pt[6], pt[7], pt[8]);
-            return;
-        }
+            });
+        timed("align_finish", 0.0, 0, [&] { launch_sa<FinishK>(SA_WAVES_PER_EU, L.s.n, L.lds.lds_bytes, A); });
+    }
+
+    // Async mode: the overflowed jobs again at the proven bound (no splits, no deferred regions, like the
+    // synchronous re-run); the waves that finished the jobs have listed them and written every other job's rows
+    // (job_final), and the re-run's write its own.  It carries the first attempt's LDS plan.
+    void enqueue_async_rerun(const SaLaunch& L, const SaSlots& s1) {
+        unsigned int* const next1 = (unsigned int*)(al->d_ctr1.p + 1);
+        SaArgs A1 = base_args(al->d_jobs1.p, al->d_order1.p, 0, next1, al->d_scratch2.p, s1);
+        lds_args(A1, L.lds);
+        async_args(A1);
+        A1.n_jobs_dev = al->d_ctr1.p;
+        timed("align_jobs_retry", 0.0, 0, [&] { launch_sa<JobsK>(SA_WAVES_PER_EU, s1.n, L.lds.lds_bytes, A1); });
+        NPGX_HIP(hipMemcpyAsync(as->epoch, d_slot_epoch, 4, hipMemcpyDeviceToDevice, st));
+    }
+
+    // Waits for the attempt and takes its jobs' results; the overflowed ones are left in p.again
+    void collect(const SaAttempt& at, AlignResult& res) {
         int32_t* pl = (int32_t*)al->pinned.take((size_t)n_jobs * 8 + 8, st);
         NPGX_HIP(hipMemcpyAsync(pl, d_job_len, ((size_t)n_jobs * 2 + 1) * 4, hipMemcpyDeviceToHost, st));
-        al->host_ms[0] += ms(tp);
+        al->host_ms[0] += ms_since(tp);
         tp = std::chrono::steady_clock::now();
         NPGX_HIP(stream_wait(st));
-        al->host_ms[1] += ms(tp);
+        al->host_ms[1] += ms_since(tp);
         tp = std::chrono::steady_clock::now();
         // (after the wait: a copy into pageable memory would wait for the
         // kernels itself and book their time as host preparation)
-        if (al->want_stats)
-            NPGX_HIP(hipMemcpy(jst.data(), al->d_job_stats.p, jst.size() * 8, hipMemcpyDeviceToHost));
-        memcpy(jlen.data(), pl, n_jobs * 4);
-        memcpy(jstat.data(), pl + n_jobs, n_jobs * 4);
+        std::vector<int64_t> jst(al->want_stats ? (size_t)n_jobs * NPGX_JOB_STATS : 0);
+        if (al->want_stats) NPGX_HIP(hipMemcpy(jst.data(), al->d_job_stats.p, jst.size() * 8, hipMemcpyDeviceToHost));
+        memcpy(p.jlen.data(), pl, n_jobs * 4);
+        memcpy(p.jstat.data(), pl + n_jobs, n_jobs * 4);
         al->epoch_base = std::max(al->epoch_base, (uint32_t)pl[2 * n_jobs] + 1);
         al->pinned.reset();
-        pmark(9);
-        std::vector<int32_t> again;
-        for (int32_t j : todo) {
-            NPGX_REQUIRE(jstat[j] >= 0 && jstat[j] <= 2, NPGX_ERR_STATE, "alignment job left unfinished");
-            if (jstat[j] == 1) {
-                again.push_back(j);
-                if (rdbg && attempt == 0) {
-                    dbg_why.resize(n_jobs, 0);
-                    dbg_why[j] = jlen[j];
+        clk.mark(9);
+        p.again.clear();
+        for (int32_t j : p.todo) {
+            NPGX_REQUIRE(p.jstat[j] >= 0 && p.jstat[j] <= 2, NPGX_ERR_STATE, "alignment job left unfinished");
+            if (p.jstat[j] == 1) {
+                p.again.push_back(j);
+                if (rdbg && at.first) {
+                    rd_why.resize(n_jobs, 0);
+                    rd_why[j] = p.jlen[j];
                 }
                 continue;
             }
             if (al->want_stats)
                 for (int q = 0; q < NPGX_JOB_STATS; q++)
                     al->job_stats[(size_t)j * NPGX_JOB_STATS + q] = jst[(size_t)j * NPGX_JOB_STATS + q];
-            res.len[j] = jlen[j];
-            res.cap[j] = jobs[j].cap;
+            res.len[j] = p.jlen[j];
+            res.cap[j] = p.jobs[j].cap;
             // B of the job (rows [n, 2n) of its A|B|C scratch), or A (status 2)
-            res.bptr[j] = (const char*)(scr.p + jobs[j].scratch + (jstat[j] == 2 ? 0 : (int64_t)jobs[j].n * jobs[j].cap));
+            res.bptr[j] = (const char*)(at.scr->p + p.jobs[j].scratch +
+                                        (p.jstat[j] == 2 ? 0 : (int64_t)p.jobs[j].n * p.jobs[j].cap));
         }
-        if (attempt == 1 && !again.empty())
-            throw Error(NPGX_ERR_RANGE, "alignment exceeded the proven column bound");
-        if (attempt == 1 && rdbg)
-            for (int32_t j : todo)
-                fprintf(stderr, "retry job %d: rows %d longest %d residues %d room0 %d split %d length %d why %d\n", j,
-                        jobs[j].n, jmax[j], jsum[j], dbg_cap0[j], j < (int32_t)dbg_split.size() ? dbg_split[j] : -1,
-                        jlen[j], j < (int32_t)dbg_why.size() ? -dbg_why[j] : 0);
-        todo.swap(again);
     }
-    if (!wide_idx.empty()) {
+
+    // The first attempt's overflowed jobs (p.todo) again at the proven bound, in a second scratch
+    void rerun(AlignResult& res) {
+        if (rdbg) {
+            rd_cap0.assign(n_jobs, 0);
+            for (int32_t j : p.todo) rd_cap0[j] = p.jobs[j].cap;
+        }
+        const SaAttempt at{"align_jobs_retry", &al->d_scratch2, size_proven(p.jobs, p.todo), false};
+        clk.mark(2);
+        plan_whole_queue();
+        enqueue_jobs(at, nullptr);
+        clk.mark(8);
+        collect(at, res);
+        if (!p.again.empty()) throw Error(NPGX_ERR_RANGE, "alignment exceeded the proven column bound");
+        if (rdbg)
+            for (int32_t j : p.todo)
+                fprintf(stderr, "retry job %d: rows %d longest %d residues %d room0 %d split %d length %d why %d\n", j,
+                        p.jobs[j].n, p.jmax[j], p.jsum[j], rd_cap0[j], p.is_split[j], p.jlen[j],
+                        j < (int32_t)rd_why.size() ? -rd_why[j] : 0);
+    }
+
+    // the problems of more than 64 rows (wide_aligner.hip)
+    void run_wide(AlignResult& res) {
+        const npgx_align_options& o = al->opt;
         if (!al->wide) al->wide = wide_create();
-        const int params[5] = {o.mismatch_check, o.gap_check, o.aligned_check, o.min_length, wf};
+        const int params[5] = {o.mismatch_check, o.gap_check, o.aligned_check, o.min_length, P.wf};
         std::vector<int32_t> wl, wc;
         std::vector<const char*> wp;
         auto ti = al->timer.begin("align_wide", st, 0.0, 0);
         double wide_wait = 0;  // booked as kernel wait, not host preparation
-        align_wide(al->wide, st, d_rows, ne_off.data(), ne_len.data(), (int64_t)ne_len.size(), wide_in, params,
+        align_wide(al->wide, st, d_rows, p.ne_off.data(), p.ne_len.data(), (int64_t)p.ne_len.size(), p.wide_in, params,
                    o.aligner_type, wl, wc, wp, &wide_wait);
         al->timer.end(ti, st);
         al->host_ms[1] += wide_wait;
         tp += std::chrono::duration_cast<std::chrono::steady_clock::duration>(
             std::chrono::duration<double, std::milli>(wide_wait));
-        for (size_t q = 0; q < wide_idx.size(); q++) {
-            res.len[wide_idx[q]] = wl[q];
-            res.cap[wide_idx[q]] = wc[q];
-            res.bptr[wide_idx[q]] = wp[q];
+        for (size_t q = 0; q < p.wide_idx.size(); q++) {
+            res.len[p.wide_idx[q]] = wl[q];
+            res.cap[p.wide_idx[q]] = wc[q];
+            res.bptr[p.wide_idx[q]] = wp[q];
         }
     }
-    al->host_ms[0] += ms(tp);
-    pmark(10);
-    if (pdbg)
-        fprintf(stderr, "align_device %d jobs: prep %.3f order %.3f puts %.3f split_plan %.3f slots %.3f args %.3f "
-                "lds+split %.3f launch %.3f post %.3f wait %.3f results %.3f ms\n", n_jobs, pt[0], pt[1], pt[2],
-                pt[3], pt[4], pt[5], pt[6], pt[7], pt[8], pt[9], pt[10]);
+};
+
+// NPGX_SPLIT_DEBUG (tools/split_stats.py sets and clears it at run time): the
+// sync states and segment results of the launches just enqueued, to stderr
+static void split_debug(npgx_aligner* al, hipStream_t st, int32_t n_jobs, const SaArgs& A, bool deferring) {
+    const SaPlan& p = al->plan;
+    const std::vector<SaJob>& jobs = p.jobs;
+    const std::vector<SaSplit>& splits = p.splits;
+    const std::vector<SaSeg>& segs = p.segs;
+    const std::vector<int32_t>&jmax = p.jmax, &todo = p.todo;
+    std::vector<int32_t> tg((size_t)p.n_tgt);
+    std::vector<int4> sr(segs.size());
+    NPGX_HIP(hipMemcpyAsync(tg.data(), al->d_targets.p, tg.size() * 4, hipMemcpyDeviceToHost, st));
+    NPGX_HIP(hipMemcpyAsync(sr.data(), al->d_seg_res.p, sr.size() * 16, hipMemcpyDeviceToHost, st));
+    NPGX_HIP(hipStreamSynchronize(st));
+    for (const SaSplit& sp : splits) {
+        const int n = jobs[sp.job].n;
+        int valid = 0, ovf = 0, hits = 0;
+        for (int k = 1; k < sp.K; k++) valid += tg[sp.tgt + (int64_t)(k - 1) * n] >= 0;
+        std::string chain;
+        for (int k = 0; k < sp.K; k++) {
+            const int4 r = sr[sp.seg0 + k];
+            ovf += r.z;
+            hits += r.x >= 0 && r.x < sp.K;
+        }
+        for (int k = 0, guard = 0; k < sp.K && k >= 0 && guard < 1000; guard++) {
+            const int4 r = sr[sp.seg0 + k];
+            chain += std::to_string(k) + "(" + std::to_string(r.y) + (r.z ? "!" : "") + ")>";
+            if (r.x <= k) break;
+            k = r.x;
+        }
+        fprintf(stderr, "split job %d n=%d K=%d maxlen=%d valid_states=%d hits=%d ovf=%d chain %s\n", sp.job,
+                n, sp.K, jmax[sp.job], valid, hits, ovf, chain.c_str());
+    }
+    // per job, when its own walk or its last segment ended in k_align_jobs
+    // (wall clock; the sub-job launch below sets its sub-jobs beside it)
+    std::vector<int64_t> walk_end;
+    int64_t crit_t0 = INT64_MAX;
+    if (al->want_stats) {  // the slowest segments (wall clock at 100 MHz)
+        std::vector<int64_t> sw(2 * segs.size());
+        NPGX_HIP(hipMemcpy(sw.data(), al->d_seg_wall.p, sw.size() * 8, hipMemcpyDeviceToHost));
+        std::vector<std::pair<int64_t, int>> d;
+        for (size_t q = 0; q < segs.size(); q++) d.push_back({sw[2 * q + 1] - sw[2 * q], (int)q});
+        std::sort(d.rbegin(), d.rend());
+        for (size_t q = 0; q < std::min<size_t>(5, d.size()); q++) {
+            const int4 r = sr[(size_t)d[q].second];
+            fprintf(stderr, "slow segment %d: %.1f us, %d cols, next %d (K %d), n %d\n", d[q].second,
+                    d[q].first / 100.0, r.y, r.x, splits[segs[(size_t)d[q].second].split].K,
+                    jobs[splits[segs[(size_t)d[q].second].split].job].n);
+        }
+        // the launch's critical path: when the segments and the whole jobs end
+        std::vector<int64_t> js((size_t)n_jobs * NPGX_JOB_STATS);
+        NPGX_HIP(hipMemcpy(js.data(), al->d_job_stats.p, js.size() * 8, hipMemcpyDeviceToHost));
+        int64_t t0 = INT64_MAX, se = 0, je = 0, jd = 0;
+        int jslow = -1;
+        walk_end.assign(n_jobs, 0);
+        for (size_t q = 0; q < segs.size(); q++) {
+            t0 = std::min(t0, sw[2 * q]);
+            se = std::max(se, sw[2 * q + 1]);
+            int64_t& we = walk_end[splits[segs[q].split].job];
+            we = std::max(we, sw[2 * q + 1]);
+        }
+        std::vector<uint8_t> was_split(n_jobs, 0);
+        for (const SaSplit& sp2 : splits) was_split[sp2.job] = 1;
+        for (int32_t j : todo) {
+            const int64_t* r = js.data() + (size_t)j * NPGX_JOB_STATS;
+            if (was_split[j] || r[11] <= 0 || r[23] <= 0) continue;
+            t0 = std::min(t0, r[11]);
+            je = std::max(je, r[23]);
+            walk_end[j] = r[23];
+            if (r[23] - r[11] > jd) {
+                jd = r[23] - r[11];
+                jslow = j;
+            }
+        }
+        if (t0 != INT64_MAX)
+            fprintf(stderr, "launch: segments end at %.1f us, whole jobs at %.1f us; slowest whole job %d: "
+                    "%.1f us, %lld cols, %d rows (process_seqs %.1f us, regions+realign %.1f us)\n",
+                    (se - t0) / 100.0, (je - t0) / 100.0, jslow, jd / 100.0,
+                    jslow >= 0 ? (long long)js[(size_t)jslow * NPGX_JOB_STATS + 1] : 0ll,
+                    jslow >= 0 ? jobs[jslow].n : 0,
+                    jslow >= 0 ? js[(size_t)jslow * NPGX_JOB_STATS + 8] / 2400.0 : 0.0,
+                    jslow >= 0 ? js[(size_t)jslow * NPGX_JOB_STATS + 9] / 2400.0 : 0.0);
+        crit_t0 = t0;
+    }
+    if (deferring) {  // sub-jobs: count and widths
+        unsigned long long al2[2];
+        NPGX_HIP(hipMemcpy(al2, al->d_alloc.p, 16, hipMemcpyDeviceToHost));
+        std::vector<SaSub> sb((size_t)al2[1]);
+        std::vector<int2> rs((size_t)al2[1]);
+        if (!sb.empty()) {
+            NPGX_HIP(hipMemcpy(sb.data(), al->d_subs.p, sb.size() * sizeof(SaSub), hipMemcpyDeviceToHost));
+            NPGX_HIP(hipMemcpy(rs.data(), al->d_sub_res.p, rs.size() * 8, hipMemcpyDeviceToHost));
+        }
+        if (al->want_stats && A.sub_wall && !sb.empty()) {  // the sub-job launch's critical path
+            std::vector<int64_t> sw2(2 * sb.size());
+            NPGX_HIP(hipMemcpy(sw2.data(), al->d_sub_wall.p, sw2.size() * 8, hipMemcpyDeviceToHost));
+            unsigned int sc2[SC_N];
+            NPGX_HIP(hipMemcpy(sc2, al->d_sctr.p, sizeof(sc2), hipMemcpyDeviceToHost));
+            std::vector<int64_t> segw(2 * (size_t)std::max(1, A.cap_segs));
+            NPGX_HIP(hipMemcpy(segw.data(), al->d_seg_wall.p, segw.size() * 8, hipMemcpyDeviceToHost));
+            int64_t t0 = INT64_MAX, wend = 0, send = 0, wmax = 0;
+            int wslow = -1;
+            for (size_t q = 0; q < sb.size(); q++)
+                if (sw2[2 * q] > 0) {
+                    t0 = std::min(t0, sw2[2 * q]);
+                    wend = std::max(wend, sw2[2 * q + 1]);
+                    if (sw2[2 * q + 1] - sw2[2 * q] > wmax) {
+                        wmax = sw2[2 * q + 1] - sw2[2 * q];
+                        wslow = (int)q;
+                    }
+                }
+            for (unsigned int q = (unsigned int)segs.size(); q < std::min(sc2[SC_SEGS], (unsigned)A.cap_segs); q++)
+                if (segw[2 * q] > 0) {
+                    t0 = std::min(t0, segw[2 * q]);
+                    send = std::max(send, segw[2 * q + 1]);
+                }
+            // the pair's critical path by job: each job with sub-jobs, and
+            // the job that ends either launch (tools/split_stats.py)
+            if (crit_t0 != INT64_MAX && !walk_end.empty()) {
+                const size_t nsg = std::min<size_t>(sc2[SC_SEGS], (size_t)A.cap_segs);
+                const size_t nsp = std::min<size_t>(sc2[SC_SPLITS], (size_t)A.cap_splits);
+                std::vector<SaSeg> dsg(nsg);
+                std::vector<SaSplit> dsp(nsp);
+                if (nsg) NPGX_HIP(hipMemcpy(dsg.data(), al->d_segs.p, nsg * sizeof(SaSeg), hipMemcpyDeviceToHost));
+                if (nsp) NPGX_HIP(hipMemcpy(dsp.data(), al->d_splits.p, nsp * sizeof(SaSplit), hipMemcpyDeviceToHost));
+                std::vector<int64_t> s_start(n_jobs, INT64_MAX), s_end(n_jobs, 0);
+                std::vector<int> s_cnt(n_jobs, 0);
+                for (size_t q = 0; q < sb.size(); q++) {
+                    const int32_t j = sb[q].job;
+                    if (j < 0 || j >= n_jobs) continue;
+                    s_cnt[j]++;
+                    if (sw2[2 * q] <= 0) continue;  // (split: its segments below)
+                    s_start[j] = std::min(s_start[j], sw2[2 * q]);
+                    s_end[j] = std::max(s_end[j], sw2[2 * q + 1]);
+                }
+                for (size_t q = segs.size(); q < nsg; q++) {
+                    if (segw[2 * q] <= 0 || dsg[q].split < 0 || (size_t)dsg[q].split >= nsp) continue;
+                    const int32_t sub = dsp[(size_t)dsg[q].split].sub;
+                    if (sub < 0 || (size_t)sub >= sb.size()) continue;
+                    const int32_t j = sb[(size_t)sub].job;
+                    if (j < 0 || j >= n_jobs) continue;
+                    s_start[j] = std::min(s_start[j], segw[2 * q]);
+                    s_end[j] = std::max(s_end[j], segw[2 * q + 1]);
+                }
+                int j_jobs = -1, j_subs = -1;
+                for (int32_t j = 0; j < n_jobs; j++) {
+                    if (walk_end[j] > 0 && (j_jobs < 0 || walk_end[j] > walk_end[j_jobs])) j_jobs = j;
+                    if (s_end[j] > 0 && (j_subs < 0 || s_end[j] > s_end[j_subs])) j_subs = j;
+                }
+                for (int32_t j = 0; j < n_jobs; j++)
+                    if (s_end[j] > 0)
+                        fprintf(stderr, "crit job %d: %d rows, %d cols, walk or last segment ends %.1f us; %d "
+                                "sub-jobs start %.1f us, end %.1f us\n", j, jobs[j].n, jmax[j],
+                                (walk_end[j] - crit_t0) / 100.0, s_cnt[j], (s_start[j] - crit_t0) / 100.0,
+                                (s_end[j] - crit_t0) / 100.0);
+                if (j_jobs >= 0 && j_subs >= 0)
+                    fprintf(stderr, "crit launches: k_align_jobs ends with job %d at %.1f us, k_align_sub with job "
+                            "%d at %.1f us (%s); job %d's own sub-jobs could have started at %.1f us, the "
+                            "launch's first started at %.1f us\n", j_jobs, (walk_end[j_jobs] - crit_t0) / 100.0,
+                            j_subs, (s_end[j_subs] - crit_t0) / 100.0,
+                            j_jobs == j_subs ? "the same job" : "another job", j_subs,
+                            (walk_end[j_subs] - crit_t0) / 100.0, (t0 - crit_t0) / 100.0);
+            }
+            if (t0 != INT64_MAX)
+                fprintf(stderr, "sub launch: %u sub segments end at %.1f us, whole subs at %.1f us; slowest whole "
+                        "sub %d: %.1f us, %d cols, %d rows\n", sc2[SC_SEGS] - (unsigned)segs.size(),
+                        send ? (send - t0) / 100.0 : 0.0, (wend - t0) / 100.0, wslow, wmax / 100.0,
+                        wslow >= 0 ? rs[(size_t)wslow].x : 0, wslow >= 0 ? jobs[sb[(size_t)wslow].job].n : 0);
+        }
+        std::vector<int> wd;
+        for (const int2& r : rs) wd.push_back(r.x);
+        std::sort(wd.begin(), wd.end());
+        long long tot = 0;
+        for (int x : wd) tot += x;
+        fprintf(stderr, "subs %zu total_cols %lld p50 %d p90 %d p99 %d max %d\n", wd.size(), tot,
+                wd.empty() ? 0 : wd[wd.size() / 2], wd.empty() ? 0 : wd[wd.size() * 9 / 10],
+                wd.empty() ? 0 : wd[wd.size() * 99 / 100], wd.empty() ? 0 : wd.back());
+    }
+}
+
+// Device-resident batch: row r of the batch is d_rows[row_off[r] .. +row_len[r])
+// (host arrays describing device memory).  Results stay on the device: job j's
+// non-empty row k is at res.bptr[j] + k*res.cap[j] for res.len[j] columns.
+//
+// Every job first gets a room of 2 * longest row + 64 columns; the ones that
+// overflow it re-run at the proven bound -- after a host wait, or with `as`
+// from a list the device makes, enqueued at once.
+void align_device(npgx_aligner* al, const char* d_rows, const int64_t* row_off, const int32_t* row_len,
+                  const int32_t* job_row_start, int32_t n_jobs, AlignResult& res, const AlignAsync* as) {
+    NPGX_HIP(hipSetDevice(al->device));
+    NPGX_REQUIRE(n_jobs >= 0, NPGX_ERR_ARG, "n_jobs < 0");
+    static const bool pdbg = getenv("NPGX_PREP_DEBUG") != nullptr;
+    static const bool rdbg = getenv("NPGX_RETRY_DEBUG") != nullptr;
+    const npgx_align_options& o = al->opt;
+    SaPlan& p = al->plan;
+    const auto now = std::chrono::steady_clock::now();
+    SaCall c{al, p, al->stream, as, as ? as->ujobs : nullptr, n_jobs, d_rows,
+             Params{o.mismatch_check, o.gap_check, o.aligned_check, o.min_length, weight_factor(o.min_identity_x1e4),
+                    al->long_head, al->long_m},
+             now, PrepClock{pdbg, {0}, now}, rdbg};
+    c.plan_batch(row_off, row_len, job_row_start, res);
+    p.todo = p.order;
+    SaSlots s1;  // async mode: the re-run's slots, held by the first attempt's buffers too
+    if (as) s1 = c.plan_async_rerun();
+    if (!p.todo.empty()) {
+        const SaAttempt first{"align_jobs", &al->d_scratch, p.first, true};
+        c.clk.mark(2);
+        c.plan_splits();
+        c.plan_twins();
+        const SaLaunch L = c.enqueue_jobs(first, as ? &s1 : nullptr);
+        c.enqueue_deferred(L);
+        if (!p.splits.empty() && getenv("NPGX_SPLIT_DEBUG")) split_debug(al, c.st, n_jobs, L.A, L.deferring);
+        c.clk.mark(8);
+        if (as) {
+            c.enqueue_async_rerun(L, s1);
+            res.len.clear();
+            res.cap.clear();
+            res.bptr.clear();
+            al->host_ms[0] += ms_since(c.tp);
+            c.clk.mark(8);
+            c.clk.report(n_jobs, true);
+            return;
+        }
+        c.collect(first, res);
+        p.todo.swap(p.again);
+        if (!p.todo.empty()) c.rerun(res);
+    }
+    if (!p.wide_idx.empty()) c.run_wide(res);
+    al->host_ms[0] += ms_since(c.tp);
+    c.clk.mark(10);
+    c.clk.report(n_jobs, false);
 }
 
 // n_retried non-null: through align_device's async mode (the form the device
