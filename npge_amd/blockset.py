@@ -101,6 +101,9 @@ SMTH_COUNT_NAMES = ["map_bytes", "row_bytes", "blocks_cut", "pieces"]
 MERGE_UNIQUE_COUNT_NAMES = ["blocks_inspected", "merges", "fragments_merged"]
 REFINE_COUNT_NAMES = ["jobs", "long_jobs", "chunks", "longest_chunk", "columns_in", "columns_out"]
 REALIGN_COUNT_NAMES = ["candidates", "replaced", "filter_refused", "not_better"]
+# STAGE_NAMES, GPU_STAGE_NAMES and COUNTER_NAMES name npgx_bb_stats' ms_stage, ms_gpu and counters by
+# position: the enums Stage, GpuStage and Counter in csrc/common.hpp are the same lists in the same order,
+# and must follow any change here
 STAGE_NAMES = ["anchor_finder", "stem_dummy", "move_unchanged", "flank_gather", "align_batch",
                "stitch", "fix_ends", "overlapless_union", "blockset_hash", "filter",
                "align_host_prep", "device_wait", "fix_ends_device", "fix_ends_slice",

@@ -30,6 +30,27 @@ struct Error : std::runtime_error {
 
 void set_last_error(const std::string& msg);
 
+// The ids of npgx_bb_stats' arrays (include/npge_amd.h says what each holds).
+// Python names them by position: the order here is the order of STAGE_NAMES,
+// GPU_STAGE_NAMES and COUNTER_NAMES in npge_amd/blockset.py, and those lists
+// must follow any change here.
+enum Stage {  // ms_stage
+    ST_ANCHOR_FINDER, ST_STEM_DUMMY, ST_MOVE_UNCHANGED, ST_FLANK_GATHER, ST_ALIGN_BATCH, ST_STITCH, ST_FIX_ENDS,
+    ST_OVERLAPLESS_UNION, ST_BLOCKSET_HASH, ST_FILTER, ST_ALIGN_HOST_PREP, ST_DEVICE_WAIT, ST_FIX_ENDS_DEVICE,
+    ST_FIX_ENDS_SLICE, ST_OU_ORDER, ST_OU_ADMIT, ST_COUNT
+};
+enum GpuStage {  // ms_gpu (the stage clock's marks)
+    GS_ANCHOR_FINDER, GS_STEM_DUMMY, GS_ELF_UPLOAD, GS_ELF_PLAN, GS_FLANK_DECODE, GS_ALIGN, GS_STITCH, GS_FIX_ENDS,
+    GS_OVERLAPLESS_UNION, GS_ELF_DOWNLOAD, GS_FILTER, GS_EXTEND_LOOP_HOST, GS_COUNT
+};
+enum Counter {  // counters
+    CT_BLOCKS_AFTER_EXTEND, CT_FILTER_WHOLE, CT_FILTER_SLICES, CT_BLOCKS_AFTER_FILTER, CT_OU_IN, CT_OU_REJECTED,
+    CT_HASHES, CT_SPARE, CT_COUNT
+};
+static_assert(ST_COUNT == sizeof(npgx_bb_stats::ms_stage) / sizeof(double), "Stage / npgx_bb_stats.ms_stage");
+static_assert(GS_COUNT == sizeof(npgx_bb_stats::ms_gpu) / sizeof(double), "GpuStage / npgx_bb_stats.ms_gpu");
+static_assert(CT_COUNT == sizeof(npgx_bb_stats::counters) / sizeof(int64_t), "Counter / npgx_bb_stats.counters");
+
 // Waits for a stream by polling (hipStreamQuery) instead of the runtime's
 // blocking wait: the host thread is dedicated to the pipeline, and a blocking
 // wait costs an interrupt and a thread wake-up (tens of microseconds) at each
@@ -98,6 +119,12 @@ struct DevBuf {
     }
     // ensure() with 1.5x headroom for buffers whose size varies from call to call
     T* grow(size_t n) { return ensure(n > cap ? std::max(n, cap + cap / 2) : n); }
+    // for buffers that grow with the blocks from call to call: past the
+    // capacity, to at least twice it (`want`: what to ask for then, where the
+    // caller adds headroom to n).  Every hipFree / hipMalloc of a large buffer
+    // waits for the device and maps pages (the consensus loop of AnchorLoopFast
+    // would grow them every iteration)
+    T* grow2(size_t n, size_t want = 0) { return n > cap ? ensure(std::max(std::max(n, want), 2 * cap)) : p; }
     void swap(DevBuf& o) {
         std::swap(p, o.p);
         std::swap(cap, o.cap);

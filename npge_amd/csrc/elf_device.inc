@@ -1642,11 +1642,14 @@ static void elf_static(npgx_blockset* B, ElfDev& D) {
 }
 
 // host blocks -> table t (asynchronous; staging in D.hio, valid until the
-// next sync)
-static void dt_upload(npgx_blockset* B, ElfDev& D, int t, const std::vector<Block>& v, int64_t& nb, int64_t& nfr) {
+// next sync); reserve: a run starts on them, with dt_reserve's capacities
+static void dt_reserve(ElfDev& D, int64_t nb, int64_t nfr);
+static void dt_upload(npgx_blockset* B, ElfDev& D, int t, const std::vector<Block>& v, int64_t& nb, int64_t& nfr,
+                      bool reserve = false) {
     nb = (int64_t)v.size();
     nfr = 0;
     for (const Block& b : v) nfr += (int64_t)b.f.size();
+    if (reserve) dt_reserve(D, nb, nfr);
     const size_t bb = (size_t)nb * sizeof(DBlk), fbytes = (size_t)nfr * sizeof(DFrag);
     const size_t fo = (bb + 63) & ~(size_t)63;
     char* st = D.hio.ensure(fo + fbytes + 64);
@@ -1674,7 +1677,6 @@ static void dt_upload(npgx_blockset* B, ElfDev& D, int t, const std::vector<Bloc
 // then runs).  nb / nfr: the stem blocks and their fragments; *groups: the
 // AnchorFinder's blocks (groups of two or more FoundFragments)
 static ElfDev& elf_dev(npgx_blockset* B);
-static void dt_reserve(ElfDev& D, int64_t nb, int64_t nfr);
 static bool anchors_to_device(npgx_blockset* B, npgx_af* af, int64_t& nb, int64_t& nfr, int64_t* groups) {
     AfDevKeys K;
     if (!af_device_keys(af, &K)) return false;
@@ -1840,45 +1842,19 @@ static void run_pass(npgx_blockset* B, ElfDev& D, const P& p, int64_t bound) {
     }
 }
 
+template <class... Bufs>
+static void ensure_all(size_t n, Bufs&... bufs) {
+    (bufs.ensure(n), ...);
+}
 // capacities for a table of nb blocks and nfr fragments (the loop never adds any)
 static void dt_reserve(ElfDev& D, int64_t nb, int64_t nfr) {
     const int64_t nb0 = std::max<int64_t>(nb, 1), nfr0 = std::max<int64_t>(nfr, 1);
-    D.tb[0].ensure((size_t)nb0);
-    D.tf[0].ensure((size_t)nfr0);
-    D.tb[1].ensure((size_t)nb0);
-    D.tf[1].ensure((size_t)nfr0);
     D.sum.ensure(1);
-    D.bplan.ensure((size_t)nb0);
-    D.jobs.ensure((size_t)(2 * nb0));
-    D.jobsum.ensure((size_t)(2 * nb0));
-    D.rows.ensure((size_t)(2 * nfr0));
-    D.row_off.ensure((size_t)(2 * nfr0));
-    D.row_len.ensure((size_t)(2 * nfr0));
-    D.res.ensure((size_t)(2 * nb0));
-    D.cj.ensure((size_t)nb0);
-    D.rowp.ensure((size_t)nfr0);
-    D.list.ensure((size_t)(2 * nb0));
-    D.se.ensure((size_t)(2 * nb0));
-    D.cnt.ensure((size_t)(2 * nfr0));
-    D.keys.ensure((size_t)nb0);
-    D.pkey.ensure((size_t)nb0);
-    D.pkey_s.ensure((size_t)nb0);
-    D.pval.ensure((size_t)nb0);
-    D.pval_s.ensure((size_t)nb0);
-    D.skeys.ensure((size_t)nb0);
-    D.sf.ensure((size_t)nfr0);
-    D.fb.ensure((size_t)nfr0);
-    D.dcnt.ensure((size_t)nb0);
-    D.dcur.ensure((size_t)nb0);
-    D.doff.ensure((size_t)nb0);
-    D.ddo.ensure((size_t)nb0);
-    D.ddc.ensure((size_t)nb0);
-    D.pri.ensure((size_t)nb0);
-    D.status.ensure((size_t)nb0);
-    D.fkey.ensure((size_t)nfr0);
-    D.fkey_s.ensure((size_t)nfr0);
-    D.fval.ensure((size_t)nfr0);
-    D.fval_s.ensure((size_t)nfr0);
+    ensure_all((size_t)nb0, D.tb[0], D.tb[1], D.bplan, D.cj, D.keys, D.skeys, D.pkey, D.pkey_s, D.pval, D.pval_s,
+               D.dcnt, D.dcur, D.doff, D.ddo, D.ddc, D.pri, D.status);
+    ensure_all((size_t)(2 * nb0), D.jobs, D.jobsum, D.res, D.list, D.se);
+    ensure_all((size_t)nfr0, D.tf[0], D.tf[1], D.rowp, D.sf, D.fb, D.fkey, D.fkey_s, D.fval, D.fval_s);
+    ensure_all((size_t)(2 * nfr0), D.rows, D.row_off, D.row_len, D.cnt);
     D.hs.ensure((size_t)nfr0 * (size_t)D.per_frag);
     if (D.deps_cap < 8 * nfr0 + (1 << 20)) {
         D.deps_cap = 8 * nfr0 + (1 << 20);
@@ -1999,11 +1975,26 @@ static void dt_check(npgx_blockset* B, ElfDev& D, int t, const ElfSum& S, int it
     }
 }
 
-// OverlaplessUnion of table t (counts nb1 / nfr1 in the summary, at most
-// nb / nfr) into table t ^ 1 (counts nb / nfr in the summary); ES_OU_HOST or
-// ES_OU_CAP in the summary: not done, the host must run it
-static void dt_ou_launch(npgx_blockset* B, ElfDev& D, int t, int64_t nb, int64_t nfr) {
-    hipStream_t st = B->stream;
+// a zeroed summary with these counts to D.sum: nb / nfr, the table the tail
+// reads, or (ou_input) nb1 / nfr1, the table OverlaplessUnion reads
+static void sum_upload(npgx_blockset* B, ElfDev& D, int64_t nb, int64_t nfr, bool ou_input = false) {
+    ElfSum* hs = (ElfSum*)B->pinned.take(sizeof(ElfSum), B->stream);
+    *hs = ElfSum{};
+    (ou_input ? hs->nb1 : hs->nb) = nb;
+    (ou_input ? hs->nfr1 : hs->nfr) = nfr;
+    NPGX_HIP(hipMemcpyAsync(D.sum.p, hs, sizeof(ElfSum), hipMemcpyHostToDevice, B->stream));
+}
+
+// ES_OU_CAP: more conflicts than the dependency list holds (the host ran
+// this OverlaplessUnion); the next one gets a list four times as long
+static void deps_grow_if_full(ElfDev& D, const ElfSum& S) {
+    if (!(S.flags & ES_OU_CAP)) return;
+    D.deps_cap *= 4;
+    D.deps.ensure((size_t)D.deps_cap);
+}
+
+// OverlaplessUnion's arguments: table t (at most nb blocks / nfr fragments) into table t ^ 1
+static OuArgs ou_args(ElfDev& D, int t, int64_t nb, int64_t nfr) {
     OuArgs oa;
     oa.tb = D.tb[t].p;
     oa.tf = D.tf[t].p;
@@ -2034,6 +2025,15 @@ static void dt_ou_launch(npgx_blockset* B, ElfDev& D, int t, int64_t nb, int64_t
     oa.ob = D.tb[t ^ 1].p;
     oa.of = D.tf[t ^ 1].p;
     oa.sum = D.sum.p;
+    return oa;
+}
+
+// OverlaplessUnion of table t (counts nb1 / nfr1 in the summary, at most
+// nb / nfr) into table t ^ 1 (counts nb / nfr in the summary); ES_OU_HOST or
+// ES_OU_CAP in the summary: not done, the host must run it
+static void dt_ou_launch(npgx_blockset* B, ElfDev& D, int t, int64_t nb, int64_t nfr) {
+    hipStream_t st = B->stream;
+    const OuArgs oa = ou_args(D, t, nb, nfr);
     run_pass(B, D, OuPrepPass{oa}, nb);
     NPGX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_ou_fsort, dim3((unsigned)std::min<int64_t>(std::max<int64_t>(nb, 1), 8192)), dim3(64), 0, st,
@@ -2095,88 +2095,81 @@ struct ElfEntry {
     bool swapped;
 };
 
-static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_nb, int64_t pre_nfr);
-
-// pre_nb >= 0: table 0 already holds pre_nb blocks / pre_nfr fragments with
-// their rows in arena[cur] (anchors_to_device); B->blocks is empty then, and
-// stays empty on a failure
-static void extend_loop_fast_dev(npgx_blockset* B, int64_t pre_nb = -1, int64_t pre_nfr = 0) {
-    ElfEntry E{B->cur, B->used, false};
-    try {
-        extend_loop_fast_dev_run(B, E, pre_nb, pre_nfr);
-    } catch (...) {
-        // the set keeps its blocks as they came in; the aligner's word tables
-        // are cleared before its next launch (launches already enqueued may
-        // have used epochs the host never heard back about)
-        if (E.swapped) B->arena[E.cur].swap(B->arena_x);
-        B->cur = E.cur;
-        B->used = E.used;
-        aligner_note_epoch(B->aligner, 0xF000);
-        throw;
-    }
-}
-
-static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_nb, int64_t pre_nfr) {
-    ElfDev& D = elf_dev(B);
-    hipStream_t st = B->stream;
-    auto t0 = Clock::now();
-    elf_static(B, D);
-    int64_t nb = pre_nb, nfr = pre_nfr;
-    int t = 0;
-    if (pre_nb < 0) {
-        nb = (int64_t)B->blocks.size();
-        nfr = 0;
-        for (const Block& b : B->blocks) nfr += (int64_t)b.f.size();
-        dt_reserve(D, nb, nfr);
-        dt_upload(B, D, 0, B->blocks, nb, nfr);
-    }
-    D.set_cap = 0;
-    D.set_n = 0;
-    {
-        ElfSum s0{};
-        s0.nb = nb;
-        s0.nfr = nfr;
-        ElfSum* hs0 = (ElfSum*)B->pinned.take(sizeof(ElfSum), st);
-        *hs0 = s0;
-        NPGX_HIP(hipMemcpyAsync(D.sum.p, hs0, sizeof(ElfSum), hipMemcpyHostToDevice, st));
-    }
-    B->clock.mark(st, 2);
-    const int2* js = nullptr;
-    double wait_ms = 0;
-    ElfSum S = elf_tail(B, D, t, nb, js, wait_ms);
-    B->pinned.reset();
-    dt_check(B, D, t, S, -1);
-    D.set_n += S.fresh;
-    std::set<uint64_t> states;
-    states.insert(S.state);
-    B->stats.ms_host += ms_since(t0);
-    const int mf = B->opt.min_fragment;
-    const int64_t mi = B->opt.min_identity_x1e4;
+// One run of the device loop (the counterpart of SaCall in
+// similar_aligner.hip): the state its steps share, and the steps in the order
+// extend_loop_fast_dev_run calls them.  Every step of an iteration books its
+// host time to its ms_stage and ends on its mark of the stage clock.
+struct ElfLoop {
+    npgx_blockset* const B;
+    ElfDev& D;
+    const hipStream_t st;
+    ElfEntry& E;
+    int t = 0;                        // the current table: a step reads it, writes the other one and flips
+    ElfSum S{};                       // the last summary downloaded ...
+    const int2* js = nullptr;         // ... and its planned jobs (rows, row length), valid until the next download
+    double wait_ms = 0;               // the host's waits for the stream so far
+    std::set<uint64_t> states;        // the Pipe's states seen
+    bool times_pending = false;       // aligner timers not read yet (async iterations)
+    const bool per_iteration_stats;   // (per-job statistics: each launch's)
+    // the iteration's values
+    int it = -1;
+    int64_t nb = 0, nfr = 0, nj = 0;  // the table's blocks and fragments, the planned jobs
+    int64_t bound = 0, maxres = 0;    // bounds: the stitched rows' bytes, the longest flank alignment
+    bool async = false;               // the aligner runs without a host wait
+    Clock::time_point t_iter;
+    double wait0 = 0, align_ms = 0;
+    // the synchronous aligner's host arrays (their capacity outlives the iteration)
     std::vector<int64_t> row_off;
     std::vector<int32_t> row_len, job_start;
-    std::vector<DRes> dres;
-    bool times_pending = false;  // aligner timers not read yet (async iterations)
-    const bool per_iteration_stats = aligner_wants_stats(B->aligner);  // (per-job statistics: each launch's)
-    for (int it = 0; it < B->opt.max_iterations || B->opt.max_iterations == -1; it++) {
+
+    ElfLoop(npgx_blockset* B_, ElfEntry& E_)
+        : B(B_), D(elf_dev(B_)), st(B_->stream), E(E_), per_iteration_stats(aligner_wants_stats(B_->aligner)) {}
+
+    void flip() { t ^= 1; }
+
+    // hash, Pipe state, MoveUnchanged and the next plan on the current table
+    // (elf_tail), with the loop's one host wait
+    void plan(int64_t nb_bound) {
+        S = elf_tail(B, D, t, nb_bound, js, wait_ms);
+        B->pinned.reset();
+        dt_check(B, D, t, S, it);
+    }
+
+    // The loop's switches and the set's names, the blocks into table 0 (pre_nb
+    // >= 0: anchors_to_device left them there), an empty MoveUnchanged set,
+    // the first summary and the first plan
+    void enter(int64_t pre_nb, int64_t pre_nfr) {
+        auto t0 = Clock::now();
+        elf_static(B, D);
+        nb = pre_nb, nfr = pre_nfr;
+        if (pre_nb < 0) dt_upload(B, D, 0, B->blocks, nb, nfr, true);
+        D.set_cap = 0;
+        D.set_n = 0;
+        sum_upload(B, D, nb, nfr);
+        B->clock.mark(st, GS_ELF_UPLOAD);
+        plan(nb);
+        D.set_n += S.fresh;
+        states.insert(S.state);
+        B->stats.ms_host += ms_since(t0);
+    }
+
+    // An iteration starts: the last plan gives its counts, the device summary
+    // starts from zero, and the planned flank rows are decoded into B->flank
+    void decode_flanks(int iteration) {
+        it = iteration;
         B->stats.iterations++;
         B->stats.device_iterations++;
-        auto ti = Clock::now();
-        const double wait0 = wait_ms;
+        t_iter = Clock::now();
+        wait0 = wait_ms;
         NPGX_REQUIRE(!(S.flags & ES_FLANK_RANGE), NPGX_ERR_RANGE, "flank too long");
-        const int64_t nj = S.nj;
+        nj = S.nj;
         nb = S.nb;
         nfr = S.nfr;
-        std::vector<int32_t> jnf((size_t)nj);
-        for (int64_t j = 0; j < nj; j++) jnf[(size_t)j] = js[j].x;
         B->stats.aligned_residues += S.flank;
         B->stats.align_jobs += nj;
         NPGX_HIP(hipMemsetAsync(D.sum.p, 0, sizeof(ElfSum), st));
-        // buffers that grow with the blocks grow geometrically: every hipFree /
-        // hipMalloc of a large buffer waits for the device and maps pages
-        // (the consensus loop of AnchorLoopFast grows them every iteration)
-        if ((size_t)std::max<int64_t>(S.flank, 1) > B->flank.cap)
-            B->flank.ensure(std::max<size_t>((size_t)S.flank, 2 * B->flank.cap));
-        B->clock.mark(st, 3);
+        B->flank.grow2((size_t)std::max<int64_t>(S.flank, 1));
+        B->clock.mark(st, GS_ELF_PLAN);
         if (S.nrows) {
             hipLaunchKernelGGL(k_dt_decode, dim3((unsigned)S.nrows, (unsigned)((S.max_sh + PIECE - 1) / PIECE)),
                                dim3(256), 0, st, D.rows.p, D.wofs.p, D.nofs.p, B->ss->words.p, B->ss->nmask.p,
@@ -2184,37 +2177,26 @@ static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_
             NPGX_HIP(hipGetLastError());
             esp(B, "flank decode");
         }
-        B->clock.mark(st, 4);
-        B->stats.ms_stage[3] += ms_since(ti);
+        B->clock.mark(st, GS_FLANK_DECODE);
+        B->stats.ms_stage[ST_FLANK_GATHER] += ms_since(t_iter);
+    }
+
+    // The flank jobs through the aligner, asynchronous where every job has at
+    // most 64 rows and the batch fits the budget; either way the results are
+    // in D.res, and bound / maxres cover them
+    void align() {
         auto ta = Clock::now();
         AlignResult& res = B->fx.res;
-        int64_t bound = S.bytes + 16 * nb + 64, maxres = 0;
+        bound = S.bytes + 16 * nb + 64;
+        maxres = 0;
         bool wide = false;
         int64_t async_bytes = 0;
         for (int64_t j = 0; j < nj; j++) {
-            wide |= jnf[(size_t)j] > 64;
+            wide |= js[j].x > 64;
             const int64_t n = js[j].x, rs = (int64_t)js[j].x * js[j].y;
             async_bytes += ((3 * n * rs + 255) & ~255ll) + n * rs;
         }
-        const bool async = nj && !wide && async_bytes <= D.env_async_budget;
-        if (nj && !async) {
-            B->stats.device_sync_iterations++;
-            // the batch's host arrays for align_device (row r of job j at base + i * sh)
-            row_off.resize((size_t)S.nrows);
-            row_len.resize((size_t)S.nrows);
-            job_start.assign(1, 0);
-            int64_t base = 0, r = 0;
-            for (int64_t j = 0; j < nj; j++) {
-                const int2 q = js[j];
-                for (int i = 0; i < q.x; i++) {
-                    row_off[(size_t)r] = base;
-                    row_len[(size_t)r] = q.y;
-                    base += q.y;
-                    r++;
-                }
-                job_start.push_back((int32_t)r);
-            }
-        }
+        async = nj && !wide && async_bytes <= D.env_async_budget;
         if (async) {
             // no host wait: the aligner re-runs overflowed jobs and writes every
             // job's rows to D.res on the device; the bounds use the proven
@@ -2237,8 +2219,10 @@ static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_
             }
             double prep = 0, wait = 0;
             aligner_host_ms(B->aligner, &prep, &wait);
-            B->stats.ms_stage[10] += prep;
+            B->stats.ms_stage[ST_ALIGN_HOST_PREP] += prep;
         } else if (nj) {
+            B->stats.device_sync_iterations++;
+            sync_rows();
             if (times_pending) collect_aligner(B);
             times_pending = false;
             aligner_timer_reset(B->aligner);
@@ -2246,38 +2230,59 @@ static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_
             collect_aligner(B);
             double prep = 0, wait = 0;
             aligner_host_ms(B->aligner, &prep, &wait);
-            B->stats.ms_stage[10] += prep;
-            B->stats.ms_stage[11] += wait;
-            dres.resize((size_t)nj);
+            B->stats.ms_stage[ST_ALIGN_HOST_PREP] += prep;
+            B->stats.ms_stage[ST_DEVICE_WAIT] += wait;
+            DRes* hr = (DRes*)B->pinned.take((size_t)nj * sizeof(DRes), st);
             for (int64_t j = 0; j < nj; j++) {
-                dres[(size_t)j] = DRes{res.bptr[(size_t)j], res.cap[(size_t)j], res.len[(size_t)j]};
-                bound += (int64_t)jnf[(size_t)j] * res.len[(size_t)j];
+                hr[j] = DRes{res.bptr[(size_t)j], res.cap[(size_t)j], res.len[(size_t)j]};
+                bound += (int64_t)js[j].x * res.len[(size_t)j];
                 maxres = std::max<int64_t>(maxres, res.len[(size_t)j]);
             }
-            DRes* hr = (DRes*)B->pinned.take((size_t)nj * sizeof(DRes), st);
-            memcpy(hr, dres.data(), (size_t)nj * sizeof(DRes));
             NPGX_HIP(hipMemcpyAsync(D.res.p, hr, (size_t)nj * sizeof(DRes), hipMemcpyHostToDevice, st));
         }
         esp(B, "align");
-        B->clock.mark(st, 5);
-        const double align_ms = ms_since(ta);
+        B->clock.mark(st, GS_ALIGN);
+        align_ms = ms_since(ta);
         B->stats.ms_align += align_ms;
-        B->stats.ms_stage[4] += align_ms;
+        B->stats.ms_stage[ST_ALIGN_BATCH] += align_ms;
+    }
+
+    // the batch's host arrays for the synchronous align_device (row r of job j at base + i * sh)
+    void sync_rows() {
+        row_off.resize((size_t)S.nrows);
+        row_len.resize((size_t)S.nrows);
+        job_start.assign(1, 0);
+        int64_t base = 0, r = 0;
+        for (int64_t j = 0; j < nj; j++) {
+            const int2 q = js[j];
+            for (int i = 0; i < q.x; i++) {
+                row_off[(size_t)r] = base;
+                row_len[(size_t)r] = q.y;
+                base += q.y;
+                r++;
+            }
+            job_start.push_back((int32_t)r);
+        }
+    }
+
+    // Every block's rows with its flank alignments on both sides, into the
+    // other arena buffer and the other table.  Never into the entry rows'
+    // buffer: before the second stitch would, that buffer is swapped out
+    // into arena_x (ElfEntry)
+    void stitch() {
         auto tr = Clock::now();
-        // stitch into the other arena buffer (never the entry rows' buffer)
         if ((B->cur ^ 1) == E.cur && !E.swapped) {
             B->arena[E.cur].swap(B->arena_x);
             E.swapped = true;
         }
         DevBuf<char>& o = B->arena[B->cur ^ 1];
-        if ((size_t)bound > o.cap) o.ensure(std::max<size_t>((size_t)bound + (size_t)bound / 4 + 4096, 2 * o.cap));
+        o.grow2((size_t)bound, (size_t)bound + (size_t)bound / 4 + 4096);
         // pieces: sum over the rows of ceil(length / PIECE) <= bytes / PIECE + rows
         const int64_t piece_cap = bound / PIECE + nfr + 1;
-        if ((size_t)piece_cap > D.pieces.cap) D.pieces.ensure(std::max<size_t>((size_t)piece_cap, 2 * D.pieces.cap));
+        D.pieces.grow2((size_t)piece_cap);
         const StitchArgs sa{D.tb[t].p, D.tf[t].p, D.tb[t ^ 1].p, D.tf[t ^ 1].p, nb, D.bplan.p, D.res.p, D.sum.p,
                             D.pieces.p};
         run_pass(B, D, StitchPass{sa}, nb);
-        const int64_t maxL = (int64_t)S.max_len + 2 * maxres + 1;
         if (nfr) {
             size_t tk = B->timer.begin("stitch_rows", st, 2.0 * (double)bound, bound);
             hipLaunchKernelGGL(k_dt_stitch_pieces, dim3((unsigned)std::min<int64_t>(piece_cap, 16384)), dim3(256), 0,
@@ -2286,28 +2291,30 @@ static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_
         }
         NPGX_HIP(hipGetLastError());
         esp(B, "stitch copy");
-        B->clock.mark(st, 6);
+        B->clock.mark(st, GS_STITCH);
         B->cur ^= 1;
         B->used = (size_t)bound;
-        t ^= 1;
+        flip();
         NPGX_REQUIRE(it != D.env_fail_iter, NPGX_ERR_STATE, "injected ExtendLoopFast failure (NPGX_TEST_FAIL_ELF)");
-        B->stats.ms_stage[5] += ms_since(tr);
-        // FixEnds
+        B->stats.ms_stage[ST_STITCH] += ms_since(tr);
+    }
+
+    // FixEnds on the stitched blocks (the job lists and tiles planned on the
+    // device), then the slicing into the other table
+    void fix_ends() {
         auto tf = Clock::now();
         const int64_t bits_bound = bound / 64 + nb + 1;
-        if ((size_t)bits_bound > D.bits.cap) D.bits.ensure(std::max<size_t>((size_t)bits_bound, 2 * D.bits.cap));
+        D.bits.grow2((size_t)bits_bound);
         D.tiles.ensure((size_t)(bits_bound / TILE_WORDS + nb + 1));
         const FePlanArgs fa{D.tb[t].p, D.tf[t].p, nb, B->base(), D.cj.p, D.rowp.p, D.tiles.p, D.list.p, D.sum.p};
         run_pass(B, D, FePass{fa}, nb);
-        FeArgs A;
+        FeArgs A = fe_args(B);
         A.jobs = D.cj.p;
         A.rowp = D.rowp.p;
         A.bits = D.bits.p;
         A.out_se = D.se.p;
         A.out_cnt = D.cnt.p;
-        A.mf = mf;
-        A.min_good = (int)(mi * mf / 10000);
-        A.sub_frame = (int)((10000 - mi) * mf / 10000);
+        const int64_t maxL = (int64_t)S.max_len + 2 * maxres + 1;
         A.lds_words = (int)std::min<int64_t>((maxL + 63) / 64, 4096);
         const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nb, 2048));
         size_t tk = B->timer.begin("fix_ends", st, 0.0, 0);
@@ -2319,60 +2326,38 @@ static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_
         B->timer.end(tk, st);
         NPGX_HIP(hipGetLastError());
         esp(B, "fix_ends");
-        const SliceArgs sl{D.tb[t].p, D.tf[t].p, D.tb[t ^ 1].p, D.tf[t ^ 1].p, nb, D.se.p, D.cnt.p, mf, B->base(),
+        const SliceArgs sl{D.tb[t].p, D.tf[t].p, D.tb[t ^ 1].p, D.tf[t ^ 1].p, nb, D.se.p, D.cnt.p, A.mf, B->base(),
                            D.wofs.p, D.nofs.p, B->ss->words.p, B->ss->nmask.p, D.sum.p};
         run_pass(B, D, SlicePass{sl}, nb);
         NPGX_HIP(hipGetLastError());
-        B->clock.mark(st, 7);
-        t ^= 1;
-        B->stats.ms_stage[6] += ms_since(tf);
-        // OverlaplessUnion
+        B->clock.mark(st, GS_FIX_ENDS);
+        flip();
+        B->stats.ms_stage[ST_FIX_ENDS] += ms_since(tf);
+    }
+
+    // OverlaplessUnion --ou-move of the sliced table into the other one
+    void overlapless_union() {
         auto to = Clock::now();
         dt_ou_launch(B, D, t, nb, nfr);
-        B->clock.mark(st, 8);
-        const int t_in = t;
-        t ^= 1;
-        B->stats.ms_stage[7] += ms_since(to);
+        B->clock.mark(st, GS_OVERLAPLESS_UNION);
+        flip();
+        B->stats.ms_stage[ST_OVERLAPLESS_UNION] += ms_since(to);
+    }
+
+    // The iteration's one download: the next plan with the iteration's
+    // verdicts (OverlaplessUnion left to the host, the aligner's and the
+    // lengths' range errors).  True: the Pipe's state was seen before, the
+    // loop is done
+    bool tail() {
         auto th = Clock::now();
-        S = elf_tail(B, D, t, nb, js, wait_ms);
-        B->pinned.reset();
-        const int32_t align_err = S.align_err;
+        plan(nb);
+        const int32_t align_err = S.align_err, len_err = S.flags & ES_LEN_RANGE;
         if (async) aligner_note_epoch(B->aligner, S.align_epoch);
-        const int32_t len_err = S.flags & ES_LEN_RANGE;
         if (S.flags & (ES_OU_HOST | ES_OU_CAP)) {
-            // OverlaplessUnion on the host (the multiset mode, or more conflicts than the list holds)
-            if (S.flags & ES_OU_CAP) {
-                D.deps_cap *= 4;
-                D.deps.ensure((size_t)D.deps_cap);
-            }
-            B->stats.counters[7]++;  // (device loop: OverlaplessUnion runs the host took)
-            std::vector<Block> v;
-            dt_download(B, D, t_in, S.nb1, S.nfr1, v, true);
-            std::vector<uint32_t> rank(v.size());
-            {
-                uint32_t k = 0;
-                for (size_t i = 0; i < v.size(); i++)
-                    if (!v[i].held) rank[i] = k++;
-                for (size_t i = 0; i < v.size(); i++)
-                    if (v[i].held) rank[i] = k++;
-            }
-            overlapless_union(B, v, &rank);
-            for (Block& b : v) b.held = false;
-            int64_t nb2 = 0, nfr2 = 0;
-            dt_upload(B, D, t, v, nb2, nfr2);
-            ElfSum s0{};
-            s0.nb = nb2;
-            s0.nfr = nfr2;
-            ElfSum* hs0 = (ElfSum*)B->pinned.take(sizeof(ElfSum), st);
-            *hs0 = s0;
-            NPGX_HIP(hipMemcpyAsync(D.sum.p, hs0, sizeof(ElfSum), hipMemcpyHostToDevice, st));
-            S = elf_tail(B, D, t, nb2, js, wait_ms);
-            B->pinned.reset();
-            dt_check(B, D, t, S, it);
+            ou_on_host();
         } else {
-            dt_check(B, D, t, S, it);
-            B->stats.counters[4] += S.ou_in;
-            B->stats.counters[5] += S.ou_rej;
+            B->stats.counters[CT_OU_IN] += S.ou_in;
+            B->stats.counters[CT_OU_REJECTED] += S.ou_rej;
         }
         NPGX_REQUIRE(!len_err, NPGX_ERR_RANGE, "alignment too long");
         NPGX_REQUIRE(align_err == 0, NPGX_ERR_RANGE, "alignment exceeded the proven column bound");
@@ -2381,21 +2366,77 @@ static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_
             times_pending = false;
         }
         D.set_n += S.fresh;
-        B->clock.mark(st, 3);
-        B->stats.ms_stage[11] += ms_since(th);  // (the host's wait for the iteration's GPU work)
+        B->clock.mark(st, GS_ELF_PLAN);
+        B->stats.ms_stage[ST_DEVICE_WAIT] += ms_since(th);  // (the host's wait for the iteration's GPU work)
         // host bookkeeping: the iteration's wall time less the aligner and the device waits
-        B->stats.ms_host += ms_since(ti) - align_ms - (wait_ms - wait0);
+        B->stats.ms_host += ms_since(t_iter) - align_ms - (wait_ms - wait0);
         static const bool edbg = getenv("NPGX_ELF_DEBUG") != nullptr;
         if (edbg)
             fprintf(stderr, "elf(dev) it %d: ou_in %lld kept %lld state %016llx\n", it, (long long)S.ou_in,
                     (long long)S.nb, (unsigned long long)S.state);
-        if (states.count(S.state)) break;
-        states.insert(S.state);
+        return !states.insert(S.state).second;
     }
+
+    // OverlaplessUnion on the host (the multiset mode, or more conflicts than
+    // the list holds): its input, the other table, comes down with the
+    // MoveUnchanged flags, the result goes up as the current table, and the
+    // plan is made again
+    void ou_on_host() {
+        deps_grow_if_full(D, S);
+        B->stats.counters[CT_SPARE]++;  // (device loop: OverlaplessUnion runs the host took)
+        std::vector<Block> v;
+        dt_download(B, D, t ^ 1, S.nb1, S.nfr1, v, true);
+        const std::vector<uint32_t> rank = extended_first_rank(v);
+        bb::overlapless_union(B, v, &rank);  // (the host's, not the step above)
+        for (Block& b : v) b.held = false;
+        int64_t nb2 = 0, nfr2 = 0;
+        dt_upload(B, D, t, v, nb2, nfr2);
+        sum_upload(B, D, nb2, nfr2);
+        plan(nb2);
+    }
+
     // the loop's blocks back to the host
-    dt_download(B, D, t, S.nb, S.nfr, B->blocks, false);
-    if (times_pending) collect_aligner(B);  // (the download waited for the last launch)
-    B->clock.mark(st, 9);
+    void leave() {
+        dt_download(B, D, t, S.nb, S.nfr, B->blocks, false);
+        if (times_pending) collect_aligner(B);  // (the download waited for the last launch)
+        B->clock.mark(st, GS_ELF_DOWNLOAD);
+    }
+};
+
+// ExtendLoopFast's pipe on the device tables: MoveUnchanged and the flank plan
+// (enter, then every tail) -> flank decode -> align -> stitch -> FixEnds and
+// slicing -> OverlaplessUnion -> the Pipe's state check (tail)
+static void extend_loop_fast_dev_run(npgx_blockset* B, ElfEntry& E, int64_t pre_nb, int64_t pre_nfr) {
+    ElfLoop L(B, E);
+    L.enter(pre_nb, pre_nfr);
+    for (int it = 0; it < B->opt.max_iterations || B->opt.max_iterations == -1; it++) {
+        L.decode_flanks(it);
+        L.align();
+        L.stitch();
+        L.fix_ends();
+        L.overlapless_union();
+        if (L.tail()) break;
+    }
+    L.leave();
+}
+
+// pre_nb >= 0: table 0 already holds pre_nb blocks / pre_nfr fragments with
+// their rows in arena[cur] (anchors_to_device); B->blocks is empty then, and
+// stays empty on a failure
+static void extend_loop_fast_dev(npgx_blockset* B, int64_t pre_nb = -1, int64_t pre_nfr = 0) {
+    ElfEntry E{B->cur, B->used, false};
+    try {
+        extend_loop_fast_dev_run(B, E, pre_nb, pre_nfr);
+    } catch (...) {
+        // the set keeps its blocks as they came in; the aligner's word tables
+        // are cleared before its next launch (launches already enqueued may
+        // have used epochs the host never heard back about)
+        if (E.swapped) B->arena[E.cur].swap(B->arena_x);
+        B->cur = E.cur;
+        B->used = E.used;
+        aligner_note_epoch(B->aligner, 0xF000);
+        throw;
+    }
 }
 
 // OverlaplessUnion --ou-move of B->blocks through the device path (the
@@ -2408,30 +2449,21 @@ static bool overlapless_union_dev(npgx_blockset* B) {
     ElfDev& D = elf_dev(B);
     hipStream_t st = B->stream;
     elf_static(B, D);
-    int64_t nb = (int64_t)B->blocks.size(), nfr = 0;
-    for (const Block& b : B->blocks) nfr += (int64_t)b.f.size();
-    dt_reserve(D, nb, nfr);
-    dt_upload(B, D, 0, B->blocks, nb, nfr);
-    ElfSum* hs0 = (ElfSum*)B->pinned.take(sizeof(ElfSum), st);
-    *hs0 = ElfSum{};
-    hs0->nb1 = nb;
-    hs0->nfr1 = nfr;
-    NPGX_HIP(hipMemcpyAsync(D.sum.p, hs0, sizeof(ElfSum), hipMemcpyHostToDevice, st));
+    int64_t nb = 0, nfr = 0;
+    dt_upload(B, D, 0, B->blocks, nb, nfr, true);
+    sum_upload(B, D, nb, nfr, true);
     dt_ou_launch(B, D, 0, nb, nfr);
     ElfSum* out = (ElfSum*)B->pinned.take(sizeof(ElfSum), st);
     NPGX_HIP(hipMemcpyAsync(out, D.sum.p, sizeof(ElfSum), hipMemcpyDeviceToHost, st));
     sync(B);
     const ElfSum S = *out;
     if (S.flags & (ES_OU_HOST | ES_OU_CAP)) {
-        if (S.flags & ES_OU_CAP) {
-            D.deps_cap *= 4;
-            D.deps.ensure((size_t)D.deps_cap);
-        }
+        deps_grow_if_full(D, S);
         overlapless_union(B, B->blocks);
         return false;
     }
-    B->stats.counters[4] += S.ou_in;
-    B->stats.counters[5] += S.ou_rej;
+    B->stats.counters[CT_OU_IN] += S.ou_in;
+    B->stats.counters[CT_OU_REJECTED] += S.ou_rej;
     dt_download(B, D, 1, S.nb, S.nfr, B->blocks, false);
     return true;
 }
