@@ -384,6 +384,62 @@ def filter_edges():
             ("no_subblocks", _filter_no_subblocks()), ("flip", _flip()))
 
 
+INVALID_CASES = ("drop_then_keep", "drop_then_slice", "drop_then_gone", "drop_no_subblocks", "all_valid_control")
+
+
+def _invalid_rows(rng, n, L, burst_at=None):
+    """n rows of L columns: the last row differs from the first in every
+    column (no frame passes with it), the rows before it are equal but for 30
+    mismatching columns from burst_at on in the last of them."""
+    M = fam(rng, n, L)
+    mismatch(M, np.arange(L), row=n - 1)
+    if burst_at is not None:
+        mismatch(M, np.arange(burst_at, burst_at + 30), row=n - 2)
+    return M
+
+
+@functools.lru_cache(maxsize=None)
+def filter_invalid(name):
+    """One block whose last fragment is invalid: its sequence ends at its max
+    (`at`) or 5 letters before it (`past`), the row keeps max - min + 1
+    letters.  Filter drops that fragment and tries the rest again
+    (Filter.cpp:230-246).  invalid_result() holds each case's outcome;
+    all_valid_control leaves the sequence whole."""
+    n, L, burst_at, kw, past = {
+        "drop_then_keep": (3, 300, None, {}, 0),
+        "drop_then_slice": (3, 400, 185, {}, 5),
+        "drop_then_gone": (2, 300, None, {}, 0),
+        "drop_no_subblocks": (3, 300, None, dict(find_subblocks=0), 5),
+        "all_valid_control": (3, 400, 185, {}, None),
+    }[name]
+    S = Cases(67, kw)
+    k = S.add(_invalid_rows(S.rng, n, L, burst_at), None, name)
+    if past is not None:
+        q, _, mx = S.blocks[k][-1][:3]
+        S.seqs[q] = S.seqs[q][:mx - past]
+        assert len(S.seqs[q]) <= mx
+    return S
+
+
+def invalid_result(name):
+    """The oracle's Filter output of filter_invalid(name), its outcome
+    asserted: a case that degenerates fails here."""
+    S = filter_invalid(name)
+    want = S.result("Filter")
+    blk = S.blocks[0]
+    if name in ("drop_then_keep", "drop_no_subblocks"):
+        assert len(want) == 1 and sorted(want[0]) == sorted(blk[:2]), name
+    elif name == "drop_then_slice":
+        assert len(want) == 2 and all(len(b) == 2 and {f[0] for f in b} == {blk[0][0], blk[1][0]} for b in want), name
+    elif name == "drop_then_gone":
+        assert want == [], name
+    else:
+        other = filter_invalid("drop_then_slice")
+        assert [[f[1:] for f in b] for b in S.blocks] == [[f[1:] for f in b] for b in other.blocks]
+        assert sorted(map(sorted, want)) != sorted(map(sorted, other.result("Filter"))), name
+    return S, want
+
+
 # ---------------------------------------------------------------- sweep
 SWEEP_LENGTHS = (1, 63, 64, 65, 99, 100, 101, 127, 128, 129, 255, 256, 257, 4031, 4032, 4033, 4095, 4096, 4097,
                  4159, 4160, 8191, 8192, 8193, 16383, 16384, 16385, 33000)

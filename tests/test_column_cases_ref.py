@@ -119,6 +119,17 @@ def test_filter_long_runs_are_capped_alike():
     assert sorted(len(b[0][4]) for b in got[k]) == [2100, 2900]
 
 
+@pytest.mark.parametrize("name", cc.INVALID_CASES)
+def test_filter_invalid_outcomes(name):
+    """(test_filter_steps_gpu.py's inputs: the oracle drops the invalid
+    fragment and keeps, slices or loses the rest, as invalid_result asserts)"""
+    S, want = cc.invalid_result(name)
+    q, mn, mx = S.blocks[0][-1][:3]
+    assert (mx >= len(S.seqs[q])) == (name != "all_valid_control")
+    assert len(S.blocks[0][-1][4]) == mx - mn + 1 and 300 <= mx - mn + 1 <= 400
+    assert all(q != f[0] for b in want for f in b)
+
+
 def test_consensus_vote():
     S = cc.consensus_edges()
     assert S.blocks == sorted(S.blocks, key=cc.orc.consensus_order)
