@@ -367,12 +367,6 @@ struct JobRows {
     const char* p;
     int32_t stride, len;
 };
-// align_device without a host wait (the device ExtendLoopFast): the jobs that
-// overflow the first attempt re-run at the proven bound in the same stream
-// (their list made on the device), and every job's result goes to `out`
-// (device, one JobRows per job); `err` (device) is set when a job overflows
-// both attempts.  No job may have more than 64 non-empty rows (k_align_wide
-// is host-driven); AlignResult is left empty.
 // a sequence of an AnchorFinder run, by rank (anchor_finder.hip)
 struct SeqMeta {
     int64_t size;
@@ -396,6 +390,12 @@ struct AfDevKeys {
 void af_set_defer(npgx_af* af, bool on);
 bool af_device_keys(npgx_af* af, AfDevKeys* out);  // false: no deferred result pending
 
+// align_device with `as`: no host wait (the device ExtendLoopFast).  The jobs
+// that overflow the first attempt re-run at the proven bound in the same stream
+// (their list made on the device), and every job's result goes to `out`
+// (device, one JobRows per job); `err` (device) is set when a job overflows
+// both attempts.  No job may have more than 64 non-empty rows (k_align_wide
+// is host-driven); AlignResult is left empty.
 struct AlignAsync {
     JobRows* out;
     int32_t* err;

@@ -59,6 +59,19 @@ def test_ori_by_majority_fixture():
     assert blockset_hash(exp.blocks) == blockset_hash(src.blocks)
 
 
+def test_joiner_empty_middle_and_empty_row():
+    """The hand-made case of tests/test_align_batch_gpu.py: a link whose
+    between-texts are all empty joins without a middle; a link with one empty
+    and one seven-base text gets seven gaps in the empty one's row."""
+    from test_align_batch_gpu import SEQS, joiner_case
+    st = {}
+    got = jr.joiner(joiner_case(), SEQS, st)
+    assert st["joins"] == 2 and st["empty_rows"] == 1
+    assert got[0] == [(0, 0, 39, 1, SEQS[0][0:40]), (1, 0, 39, 1, SEQS[1][0:40])]
+    assert got[1] == [(1, 100, 139, 1, SEQS[1][100:120] + "-" * 7 + SEQS[1][120:140]),
+                      (2, 50, 96, 1, SEQS[2][50:97])]
+
+
 def test_joiner_leaves_failed_partner_inverted():
     """try_join inverts `another` on match -1 before can_join (Joiner.cpp:221-231)
     and does not turn it back when the join then fails."""
