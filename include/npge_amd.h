@@ -252,8 +252,11 @@ int npgx_align_kernel_times(const npgx_aligner* a, npgx_kernel_time* out, int32_
  * 12 columns-mode runs, 13 rows-mode equal/mismatch steps, 14 try_gap,
  * 15 try_aligned, 16 vector word building, 17 vector word compares,
  * 18 vector chunks, 19 vector calls, 20 append_end, 21 returns from
- * append_aligned (0 otherwise); 22 cycles of the region search */
-#define NPGX_JOB_STATS 24
+ * append_aligned (0 otherwise); 22 cycles of the region search; and, in the
+ * same profiling library, inside those phases the cycles of 24 write_tails,
+ * 25 the child's reversal (cm_reverse), 26 append_cols, 27 the stack's push
+ * and pop, and 28 the number of child descents (29-31 unused) */
+#define NPGX_JOB_STATS 32
 int npgx_align_job_stats(const npgx_aligner* a, int64_t* out, int64_t cap, int64_t* n);
 void npgx_aligner_free(npgx_aligner* a);
 

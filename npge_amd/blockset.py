@@ -111,7 +111,7 @@ STAGE_NAMES = ["anchor_finder", "stem_dummy", "move_unchanged", "flank_gather", 
 # npgx_bb_stats.ms_gpu: DraftPangenome's GPU timeline by stage ("stage-clock" tuning)
 GPU_STAGE_NAMES = ["anchor_finder", "stem_dummy", "elf_upload", "elf_plan", "flank_decode", "align", "stitch",
                    "fix_ends", "overlapless_union", "elf_download", "filter", "extend_loop_host"]
-JOB_STATS = 24  # NPGX_JOB_STATS
+JOB_STATS = 32  # NPGX_JOB_STATS
 COUNTER_NAMES = ["blocks_after_extend", "filter_whole", "filter_slices", "blocks_after_filter",
                  "ou_in", "ou_rejected", "hashes", "spare"]
 # AnchorLoop's npgx_bb_stats.loop (the oracle's orc_bs_anchor_loop_stats, same order)

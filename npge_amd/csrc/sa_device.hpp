@@ -151,10 +151,75 @@ __device__ __forceinline__ int ctz_ones(unsigned long long m) {
 // ------------------------------------------------------------ columns-mode helpers
 // Buffers hold row r at base + r*cap.  All lanes take part; rows loop uniformly.
 
+// Short spans.  A child of process_seqs is a few columns to a few tens of
+// columns wide, so a pass of one row (or one 64-column chunk of a row) per
+// trip uses m of 64 lanes and pays one memory round trip per row.  A span of
+// m columns of n rows with n*m <= FLAT_MAX is walked instead as elements
+// e = lane + 64*i -> (row e / m, column e % m): every load of the span is in
+// flight before the first store.  m is wave-uniform; the division is done
+// once per call (lane / m and 64 / m), the trips advance by additions.
+static constexpr int FLAT_TRIPS = 4;
+static constexpr int FLAT_MAX = 64 * FLAT_TRIPS;
+
+// x / m for 0 <= x < 2^16, 1 <= m: a reciprocal and two corrections
+__device__ __forceinline__ int div_small(int x, int m) {
+    int q = (int)((float)x * __builtin_amdgcn_rcpf((float)m));
+    q -= q * m > x ? 1 : 0;
+    q += (q + 1) * m <= x ? 1 : 0;
+    return q;
+}
+
+struct Flat {
+    int r, j;    // this lane's row and column in the current trip
+    int m, qm, rm;
+    __device__ __forceinline__ Flat(int lane, int m_) {
+        m = __builtin_amdgcn_readfirstlane(m_);
+        qm = __builtin_amdgcn_readfirstlane(div_small(64, m));
+        rm = 64 - qm * m;
+        r = div_small(lane, m);
+        j = lane - r * m;
+    }
+    __device__ __forceinline__ void next() {
+        j += rm;
+        r += qm;
+        if (j >= m) {
+            j -= m;
+            r++;
+        }
+    }
+};
+
+// One flattened pass over n rows x m columns (tot = n*m <= FLAT_MAX): every
+// element's load(row, column), then every store(row, column, value).
+template <class T, class L, class S>
+__device__ __forceinline__ void flat_pass(const WaveCtx& w, int m, int tot, L load, S store) {
+    T t[FLAT_TRIPS];
+    Flat f(w.lane, m);
+#pragma unroll
+    for (int i = 0; i < FLAT_TRIPS; i++) {
+        if (64 * i < tot && f.r < w.n) t[i] = load(f.r, f.j);
+        f.next();
+    }
+    Flat g(w.lane, m);
+#pragma unroll
+    for (int i = 0; i < FLAT_TRIPS; i++) {
+        if (64 * i < tot && g.r < w.n) store(g.r, g.j, t[i]);
+        g.next();
+    }
+    __syncthreads();
+}
+
 // rows [0,n): dst[d0 + j] = src[s0 + j] for j < len.  (row, 64-column chunk)
 // pairs four at a time: four loads in flight per lane instead of one.
 __device__ __forceinline__ void cm_copy(const WaveCtx& w, const char* src, char* dst, int cap, int s0, int d0,
                                         int len) {
+    const int tot = __builtin_amdgcn_readfirstlane(w.n * len);
+    if (len > 0 && tot <= FLAT_MAX) {
+        flat_pass<char>(
+            w, len, tot, [&](int r, int j) { return src[(size_t)r * cap + s0 + j]; },
+            [&](int r, int j, char x) { dst[(size_t)r * cap + d0 + j] = x; });
+        return;
+    }
     const int nch = (len + 63) >> 6, np = w.n * nch;
     for (int p0 = 0; p0 < np; p0 += 4) {
         char t[4];
@@ -175,6 +240,13 @@ __device__ __forceinline__ void cm_copy(const WaveCtx& w, const char* src, char*
 // rows [0,n): dst[d0 + j] = src[len - 1 - j] for j < len (a reversed copy;
 // src and dst rows of stride cap, (row, 64-column chunk) pairs four at a time)
 __device__ __forceinline__ void cm_copy_rev(const WaveCtx& w, const char* src, char* dst, int cap, int d0, int len) {
+    const int tot = __builtin_amdgcn_readfirstlane(w.n * len);
+    if (len > 0 && tot <= FLAT_MAX) {
+        flat_pass<char>(
+            w, len, tot, [&](int r, int j) { return src[(size_t)r * cap + len - 1 - j]; },
+            [&](int r, int j, char x) { dst[(size_t)r * cap + d0 + j] = x; });
+        return;
+    }
     const int nch = (len + 63) >> 6, np = w.n * nch;
     for (int p0 = 0; p0 < np; p0 += 4) {
         char t[4];
@@ -195,6 +267,24 @@ __device__ __forceinline__ void cm_copy_rev(const WaveCtx& w, const char* src, c
 // reverse columns [c0, c1) of every row in place (pairs four at a time)
 __device__ __forceinline__ void cm_reverse(const WaveCtx& w, char* base, int cap, int c0, int c1) {
     const int half = (c1 - c0) >> 1;
+    const int tot = __builtin_amdgcn_readfirstlane(w.n * half);
+    if (half > 0 && tot <= FLAT_MAX) {
+        struct Ends {
+            char x, y;
+        };
+        flat_pass<Ends>(
+            w, half, tot,
+            [&](int r, int j) {
+                const char* row = base + (size_t)r * cap;
+                return Ends{row[c0 + j], row[c1 - 1 - j]};
+            },
+            [&](int r, int j, Ends e) {
+                char* row = base + (size_t)r * cap;
+                row[c0 + j] = e.y;
+                row[c1 - 1 - j] = e.x;
+            });
+        return;
+    }
     const int nch = (half + 63) >> 6, np = w.n * nch;
     for (int p0 = 0; p0 < np; p0 += 4) {
         char x[4], y[4];
@@ -806,8 +896,10 @@ struct ProcT {
     bool stop;       // a target was reached (pos == target tm)
 #ifdef NPGX_SA_PROFILE
     // fast_run, equal/mismatch steps, try_gap, try_aligned, vector words,
-    // vector compares, chunks, calls, append_end, child return (reverse)
-    long long prof[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // vector compares, chunks, calls, append_end, child return (reverse);
+    // inside those: write_tails, cm_reverse / cm_copy, append_cols, the stack's
+    // push and pop, and the number of child descents
+    long long prof[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
 
     __device__ __forceinline__ ProcT(const WaveCtx& w_, const Params& P_, const Slot& S_, char* ob_, int cap_,
@@ -853,8 +945,10 @@ struct ProcT {
 
     // append_cols :67-77 (rows mode, a few columns)
     __device__ __forceinline__ void append_cols(int cols) {
+        SA_T0(ta);
         if (w.act)
             for (int j = 0; j < cols; j++) put(col + j, (char)ch(pos + j));
+        SA_ACC(12, ta);
         if (chk) {
             const int d = target_hit(cols);
             if (d >= 0) {  // the columns past the target are not kept
@@ -875,14 +969,40 @@ struct ProcT {
             ovf = rovf = true;
             return;
         }
+        SA_T0(tw);
         __syncthreads();
-        for (int r = 0; r < w.n; r++) {
-            const char* pr = bcast_ptr(v.p, r);
-            const int dr = bcast(v.d, r), qr = bcast(pos, r), tr = bcast(t, r);
-            char* o = ob + (size_t)r * cap + col;
-            for (int j = w.lane; j < m; j += 64) o[j] = j < tr ? pr[(ptrdiff_t)dr * (qr + j)] : '-';
+        const int tot = __builtin_amdgcn_readfirstlane(w.n * m);
+        if (m > 0 && tot <= FLAT_MAX) {  // a short tail: lanes are (row, column)
+            // (not flat_pass: every lane takes part in the shuffles that fetch
+            // the element's row view, the lanes past the span's end too)
+            char x[FLAT_TRIPS];
+            Flat f(w.lane, m);
+#pragma unroll
+            for (int i = 0; i < FLAT_TRIPS; i++) {
+                if (64 * i < tot) {
+                    const int rr = f.r < w.n ? f.r : 0;
+                    const char* pr = shfl_ptr(v.p, rr);
+                    const int dr = __shfl(v.d, rr), qr = __shfl(pos, rr), tr = __shfl(t, rr);
+                    x[i] = (f.r < w.n && f.j < tr) ? pr[(ptrdiff_t)dr * (qr + f.j)] : '-';
+                }
+                f.next();
+            }
+            Flat g(w.lane, m);
+#pragma unroll
+            for (int i = 0; i < FLAT_TRIPS; i++) {
+                if (64 * i < tot && g.r < w.n) ob[(size_t)g.r * cap + col + g.j] = x[i];
+                g.next();
+            }
+        } else {  // the long form: a row at a time, 64 columns a trip
+            for (int r = 0; r < w.n; r++) {
+                const char* pr = bcast_ptr(v.p, r);
+                const int dr = bcast(v.d, r), qr = bcast(pos, r), tr = bcast(t, r);
+                char* o = ob + (size_t)r * cap + col;
+                for (int j = w.lane; j < m; j += 64) o[j] = j < tr ? pr[(ptrdiff_t)dr * (qr + j)] : '-';
+            }
         }
         __syncthreads();
+        SA_ACC(10, tw);
         pos += w.act ? t : 0;
         col += m;
     }
@@ -1303,9 +1423,43 @@ struct ProcT {
     // append_end :323-342 -- the end walk tests 63 end offsets per pass.
     // Offset t from the row ends: E(t) = column len_i-1-t identical over rows,
     // V(t) = every pos_i < len_i-1-t; walk while (V&&E)(t) || (V&&E)(t+1).
+    //
+    // The walk ends at t* = the least t with neither (V&&E)(t) nor
+    // (V&&E)(t+1): a property of the rows alone, not of how many offsets a
+    // pass tests.  Every pass only moves t over offsets whose condition it
+    // has found true and stops at the first it has found false, so the narrow
+    // passes (lanes = (offset, row), K = 64/n offsets and every row's load in
+    // one trip, for the few columns a child's rows end with) and the wide
+    // passes (63 offsets, one row per trip) that take over from wherever the
+    // narrow ones leave t arrive at the same t*.
     __device__ __forceinline__ void append_end() {
         int t = 0;
-        while (true) {
+        bool done = false;
+        const int n = w.n;
+        if (n >= 4 && n <= 32) {
+            const int K = min(64 / n, 16);
+            const int k = div_small(w.lane, n), r = w.lane - k * n;
+            const bool in = k < K;
+            const int rr = in ? r : 0;
+            const char* pr = shfl_ptr(v.p, rr);
+            const int dr = __shfl(v.d, rr), lr = __shfl(v.len, rr), qr = __shfl(pos, rr);
+            const char* p0 = bcast_ptr(v.p, 0);
+            const int d0 = bcast(v.d, 0), l0 = bcast(v.len, 0);
+            for (int trip = 0; trip < 4 && !done; trip++) {
+                const int cp = lr - 1 - (t + k), cp0 = l0 - 1 - (t + k);
+                const int c = (in && cp >= 0) ? (unsigned char)pr[(ptrdiff_t)dr * cp] : -2;
+                const int c0 = (in && cp0 >= 0) ? (unsigned char)p0[(ptrdiff_t)d0 * cp0] : -1;
+                const unsigned long long ok = ballot(in && (r == 0 || c == c0) && qr < cp);
+                unsigned long long a = 0;  // bit q: (V&&E)(t + q), q < K
+                for (int q = 0; q < K; q++)
+                    if (((ok >> (q * n)) & w.rowmask) == w.rowmask) a |= 1ull << q;
+                const unsigned long long cond = (a | (a >> 1)) | (~0ull << (K - 1));  // bit K-1 needs the next trip
+                const int run = min(ctz_ones(cond), K - 1);
+                t += run;
+                done = run < K - 1;
+            }
+        }
+        while (!done) {
             const int j = w.lane;
             const char* p0 = bcast_ptr(v.p, 0);
             const int d0 = bcast(v.d, 0), q0 = bcast(pos, 0), l0 = bcast(v.len, 0);
@@ -1410,12 +1564,17 @@ struct ProcT {
                         ovf = true;
                         return col - col0;
                     }
+                    SA_T0(tp);
                     const size_t o = (size_t)depth * 64 + w.lane;
                     S.st_p[o] = v.p;
                     S.st_len[o] = v.len | (v.d < 0 ? (int)0x80000000 : 0);
                     S.st_pos[o] = pos;
                     if (w.lane == 0) S.st_col[depth] = col;
                     depth++;
+                    SA_ACC(13, tp);
+#ifdef NPGX_SA_PROFILE
+                    prof[14] += 1;
+#endif
                     View c;  // reversed prefixes [pos, pos+sh) (append_aligned :274-293)
                     c.p = v.p + (ptrdiff_t)v.d * (pos + sh - 1);
                     c.d = -v.d;
@@ -1439,11 +1598,14 @@ struct ProcT {
             v.len = l & 0x7fffffff;
             v.d = (l & (int)0x80000000) ? -1 : 1;
             pos = S.st_pos[o];
+            SA_ACC(13, t5);
             if (col > cap) {
                 ovf = rovf = true;
             } else {
+                SA_T0(tr);
                 __syncthreads();
                 cm_reverse(w, ob, cap, c0, col);
+                SA_ACC(11, tr);
             }
             pos += w.act ? child_len : 0;
             chk = depth == 0 && tm < tK;

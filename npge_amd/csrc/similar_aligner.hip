@@ -2247,7 +2247,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_
         }
         const long long t_job = clock64();
         const unsigned long long w_job = wall_clock64();  // constant-rate clock, for timelines
-        long long t_ph[3] = {0, 0, 0}, st_prof[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        long long t_ph[3] = {0, 0, 0}, st_prof[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         long long t_regions = 0;
         int st_regions0 = 0;
         int st_calls = 0, st_shifts = 0, st_gaps = 0, st_regions = 0, st_fast = 0;
@@ -2502,7 +2502,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_
                 t_ph[2] = clock64() - t0;
             }
 #ifdef NPGX_SA_PROFILE
-            for (int q = 0; q < 10; q++) st_prof[q] = pr.prof[q];
+            for (int q = 0; q < 15; q++) st_prof[q] = pr.prof[q];
 #endif
             st_calls = pr.n_aligned_calls;
             st_shifts = pr.n_shifts;
@@ -2549,6 +2549,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W))) void k_
             for (int q = 0; q < 10; q++) js[12 + q] = st_prof[q];
             js[22] = t_regions;
             js[23] = (int64_t)wall_clock64();
+            for (int q = 10; q < 15; q++) js[14 + q] = st_prof[q];
+            for (int q = 29; q < NPGX_JOB_STATS; q++) js[q] = 0;
         }
         __syncthreads();
     }

@@ -12,6 +12,9 @@ import numpy as np
 os.environ.setdefault("NPGX_TIMERS", "2")  # every launch timed (read at handle creation)
 
 os.environ.setdefault("NPGX_JOB_STATS", "1")  # per-job statistics (read at aligner creation)
+# the statistics come back with the host-collected batches only: every
+# aligner batch of the device loop through that path
+os.environ.setdefault("NPGX_ASYNC_BUDGET_MB", "0")
 
 from npge_amd import _capi, synth
 from npge_amd.anchor_finder import AnchorFinder
@@ -67,17 +70,30 @@ for i in order[:25]:
           round(cyc[i] / max(cols[i], 1), 1))
 # job-stat columns (include/npge_amd.h npgx_align_job_stats): 8-10 the phases
 # process_seqs / fix_bad_regions / realing_end, 11 and 23 wall-clock start and
-# end (not cycles), 12-21 the profiling build's Proc counters, 22 regions
+# end (not cycles), 12-21 the profiling build's Proc counters, 22 regions,
+# 24-28 the walk's short-span helpers (inside the phases above) and descents
 names = ["process_seqs", "fix_bad_regions", "realing_end"]
 prof_names = ["fast_run", "eq/mismatch", "try_gap", "try_aligned", "vec_words", "vec_compares",
               "vec_chunks", "vec_calls", "append_end", "child_return"]
-cols_ph = [8, 9, 10] + list(range(12, 22)) + [22]
-all_names = names + prof_names + ["regions"]
+walk_names = ["write_tails", "cm_reverse", "append_cols", "stack_push_pop", "descents"]
+cols_ph = [8, 9, 10] + list(range(12, 22)) + [22] + list(range(24, 29))
+all_names = names + prof_names + ["regions"] + walk_names
 ph = js[:, cols_ph]
 tot = ph.sum(axis=0)
 print("phase cycles (all jobs):", {n: "%.3e" % t for n, t in zip(all_names, tot)})
 for i in order[:5]:
     print("  top job phases:", {n: int(t) for n, t in zip(all_names, ph[i])})
+# the walk's table: every whole job, and the ten with the most cycles (split
+# jobs' segments and sub-jobs carry no per-task counters)
+walk = ph[:, 0] + ph[:, 1] + ph[:, 2]
+for label, sel in (("all jobs", np.arange(len(js))), ("ten longest jobs", order[:10])):
+    tw = max(float(walk[sel].sum()), 1.0)
+    print("walk phases, %s (%d): job cycles %.3e, the three phases %.3e" % (label, len(sel), cyc[sel].sum(), tw))
+    for n_, t_ in zip(all_names, ph[sel].sum(axis=0)):
+        if n_ in ("vec_chunks", "vec_calls", "descents"):
+            print("    %-16s %12d" % (n_, t_))
+        else:
+            print("    %-16s %12.3e  %5.1f %%" % (n_, t_, 100.0 * t_ / tw))
 print("cycles per column (median, p90, p99):", np.percentile(cyc / np.maximum(cols, 1), [50, 90, 99]))
 if shifts.sum():
     m = shifts > 0
