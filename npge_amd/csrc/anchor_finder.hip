@@ -646,6 +646,46 @@ static int bits_for(uint64_t v) {  // bits needed to represent values < v
     return b;
 }
 
+// npgx_af.h_pinned: eight 64-bit words of pinned host staging.  A word serves
+// several values in turn -- the host reads each before the next copy into the
+// word is enqueued -- and every value has a name of its own.
+enum Slot : int {
+    // word 0: a count downloaded alone and read at once
+    SLOT_N_RAW = 0,        // counters[0]: the hashes pass 1 collected
+    SLOT_N_UNIQUE = 0,     // counters[1]: of them, after sort + unique
+    SLOT_N_KEYS = 0,       // counters[2]: the keys of k_ff_collect (one GPU)
+    SLOT_C_LOCAL = 0,      // cut[3]: this rank's candidates in the kept groups (sharded)
+    // one GPU, pass 2
+    SLOT_LAST_KEY = 1,     // the last kept key of the sorted candidates (its group + 1 is G)
+    SLOT_CUT = 4,          // k_find_cut's words (CutWord) over all of H: words 4..6
+    // sharded
+    SLOT_BOUNDARY = 0,     // pass 1's copy of counters[0..8): SLOT_N_RAW and the three below
+    SLOT_FIRST_FOUND = 4,  // counters[4]: the range's first window is found,
+    SLOT_FIRST_HASH = 5,   // counters[5]: its hash
+    SLOT_LAST_FOUND = 6,   // counters[6]: the range's last window is found
+    SLOT_SHARD_CUT = 0,    // k_find_cut's words (CutWord): words 0..2
+};
+enum CutWord : int { CUT_G = 0, CUT_C = 1, CUT_TOTAL = 2 };  // k_find_cut's out[]: slot + CutWord
+
+// What a deferred run (npgx_af.defer_host) leaves for af_materialize,
+// af_pending_used and af_device_keys: valid while npgx_af.pending is set
+struct Pending {
+    int64_t keep = 0;  // sorted keys in cand_sorted
+    uint64_t G = 0;    // kept hashes at the front of huniq
+    int key_bits = 0, k = 0;
+    int32_t R = 0;
+    std::vector<SeqMeta> meta;
+    std::vector<int32_t> by_rank;
+};
+
+// What the FoundFragment count a deferred run owes needs (af_found_pending):
+// valid while npgx_af.found_pending is set.  A points into the run's sequence
+// set, which the caller keeps until then; the run's H is still in huniq.
+struct FoundOwed {
+    AfArgs A{};
+    int64_t nchunks = 0, windows = 0, nH = 0;
+};
+
 }  // namespace npgx
 
 using namespace npgx;
@@ -671,7 +711,7 @@ struct npgx_af {
     DevBuf<uint64_t> hseg;                 // found_collect's segmented output (packed into hraw)
     DevBuf<unsigned long long> segctr;     // its per-segment counters, 16 apart
     DevBuf<uint8_t> wmask;                 // per window: bloom_first's P test for found_collect
-    DevBuf<unsigned long long> counters;  // [0] = n_raw, [1] = n_unique
+    DevBuf<unsigned long long> counters;  // [0] collected, [1] unique, [2] keys, [4..6] sharded boundary
     DevBuf<TableSlot> tslots;
     DevBuf<uint32_t> tocc;
     DevBuf<uint32_t> counts, offsets, cursor;
@@ -680,7 +720,7 @@ struct npgx_af {
     DevBuf<uint64_t> cut;  // G, C, total
     DevBuf<uint64_t> cand, cand_sorted;
     DevBuf<unsigned char> temp;
-    uint64_t* h_pinned = nullptr;  // small host staging
+    uint64_t* h_pinned = nullptr;  // small host staging: eight words (Slot)
     PinnedBuf<uint64_t> pinned_dl;  // FoundFragment keys + H downloads
     npgx_af_stats stats{};
     bool has_result = false;
@@ -699,24 +739,17 @@ struct npgx_af {
     bool defer_host = false;
     bool pending = false;       // the last run's keys are not grouped on the host yet
     bool pending_used = false;  // ... nor their used hashes added (cleared by npgx_af_clear_used)
-    int64_t p_keep = 0;
-    uint64_t p_G = 0;
-    int p_key_bits = 0, p_k = 0;
-    int32_t p_R = 0;
-    std::vector<SeqMeta> p_meta;
-    std::vector<int32_t> p_by_rank;
-    DevBuf<int32_t> d_by_rank;   // rank -> input index (the device's key -> fragment conversion)
+    Pending deferred;           // filled where the deferred run returns, emptied by the next run
+    DevBuf<int32_t> d_by_rank;  // rank -> input index (the device's key -> fragment conversion)
     std::vector<int32_t> d_by_rank_host;  // what d_by_rank holds (uploaded when the sequence set changes)
     bool d_by_rank_valid = false;
     int64_t regroups = 0;  // deferred results grouped on the host (npgx_af_stats.host_regroups)
     // A deferred run on one GPU does not count the FoundFragments of the
     // groups past the cut (n_found_frags = -1): npgx_af_stats_get counts them
-    // when asked, over the run's windows (f_A points into the run's sequence
-    // set, which the caller keeps until then) and its H, still in huniq.  The
-    // next run drops the obligation.
+    // when asked, over the run's windows and its H.  The next run drops the
+    // obligation.
     bool found_pending = false;
-    AfArgs f_A{};
-    int64_t f_nchunks = 0, f_windows = 0, f_nH = 0;
+    FoundOwed found_owed;
 
     void ensure_temp(size_t bytes) { temp.ensure(bytes); }
 };
@@ -820,13 +853,58 @@ static void af_table_insert(npgx_af* af, const TableArgs& T, int64_t n, hipStrea
     NPGX_HIP(hipGetLastError());
 }
 
-// FoundFragments of every hash of H (npgx_af_stats.n_found_frags) for a run on
-// one GPU, whose pass 2 looks at the groups the cut can keep alone: the table
-// over all of H, k_ff_count over every window, the scan; the total goes to
-// h_pinned[6] (k_find_cut's third value), valid after the caller's stream_wait.
-static void af_found_total_enqueue(npgx_af* af, const AfArgs& A, int64_t nchunks, int64_t windows, int64_t nH) {
+// One rocPRIM primitive, called the way rocPRIM asks: `call(temp, bytes)` with
+// no temp returns the bytes it wants; af->temp is grown to them.
+template <class Call>
+static size_t prim_temp(npgx_af* af, Call call) {
+    size_t b = 0;
+    NPGX_HIP(call((void*)nullptr, b));
+    af->ensure_temp(b);
+    return b;
+}
+
+// ... and then for real, after the begin of a timer record that the caller
+// ends (it may launch more under the same name)
+template <class Call>
+static size_t prim_timed(npgx_af* af, const char* name, double bytes, int64_t units, Call call) {
+    size_t b = prim_temp(af, call);
+    const size_t ti = af->timer.begin(name, af->stream, bytes, units);
+    NPGX_HIP(call((void*)af->temp.p, b));
+    return ti;
+}
+
+// Radix sort of n keys over the bits [0, end_bit), one timer record.  (In:
+// const or not, as the caller holds the keys -- rocPRIM's kernels are
+// instantiated per input type.)
+template <class In>
+static void sort_keys(npgx_af* af, In in, size_t n, unsigned end_bit, uint64_t* out, const char* timer_name,
+                      double bytes) {
     hipStream_t st = af->stream;
-    Fills fills;
+    af->timer.end(prim_timed(af, timer_name, bytes, (int64_t)n,
+                             [&](void* t, size_t& b) {
+                                 return rocprim::radix_sort_keys(t, b, in, out, n, 0u, end_bit, st);
+                             }),
+                  st);
+}
+
+// exclusive scan counts -> offsets over the nH hashes, as prim_temp / prim_timed call it
+static auto scan_call(npgx_af* af, uint32_t* counts, uint32_t* offsets, int64_t nH) {
+    hipStream_t st = af->stream;
+    return [=](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, counts, offsets, 0u, (size_t)nH, rocprim::plus<uint32_t>(), st);
+    };
+}
+
+// FoundFragments of every hash of H and the cut: the membership table over
+// all nH hashes (its resets launched with whatever the caller put into
+// `fills`), k_ff_count over the rank's nchunks chunks (a rank without windows
+// launches none), `between` (the sharded run exchanges the counts there), the
+// exclusive scan and k_find_cut, whose three words (CutWord) are copied to
+// h_pinned[at ..]: valid after the caller's stream_wait.
+template <class Between>
+static TableArgs count_and_cut(npgx_af* af, const AfArgs& A, int64_t nchunks, int64_t windows, int64_t nH,
+                               Fills& fills, Slot at, Between between) {
+    hipStream_t st = af->stream;
     const TableArgs T = af_table_prepare(af, nH, fills);
     af->counts.ensure((size_t)nH);
     af->offsets.ensure((size_t)nH);
@@ -837,22 +915,41 @@ static void af_found_total_enqueue(npgx_af* af, const AfArgs& A, int64_t nchunks
     af_table_insert(af, T, nH, st);
     af->timer.end(ti, st);
     ti = af->timer.begin("ff_count", st, windows * (0.375 + 12.0), windows);
-    hipLaunchKernelGGL(k_ff_count, dim3((unsigned)nchunks), dim3(WG), 0, st, A, T, af->counts.p);
+    if (nchunks > 0) hipLaunchKernelGGL(k_ff_count, dim3((unsigned)nchunks), dim3(WG), 0, st, A, T, af->counts.p);
     NPGX_HIP(hipGetLastError());
     af->timer.end(ti, st);
-    size_t b3 = 0;
-    NPGX_HIP(rocprim::exclusive_scan(nullptr, b3, af->counts.p, af->offsets.p, 0u, (size_t)nH,
-                                     rocprim::plus<uint32_t>(), st));
-    af->ensure_temp(b3);
-    ti = af->timer.begin("scan_cut", st, nH * 8.0, nH);
-    NPGX_HIP(rocprim::exclusive_scan(af->temp.p, b3, af->counts.p, af->offsets.p, 0u, (size_t)nH,
-                                     rocprim::plus<uint32_t>(), st));
+    between();
+    ti = prim_timed(af, "scan_cut", nH * 8.0, nH, scan_call(af, af->counts.p, af->offsets.p, nH));
     af->cut.ensure(4);
     hipLaunchKernelGGL(k_find_cut, dim3(1), dim3(64), 0, st, af->offsets.p, af->counts.p, nH,
                        (uint64_t)af->opt.max_anchor_fragments, af->cut.p);
     NPGX_HIP(hipGetLastError());
     af->timer.end(ti, st);
-    NPGX_HIP(hipMemcpyAsync(af->h_pinned + 4, af->cut.p, 3 * 8, hipMemcpyDeviceToHost, st));
+    NPGX_HIP(hipMemcpyAsync(af->h_pinned + at, af->cut.p, 3 * 8, hipMemcpyDeviceToHost, st));
+    return T;
+}
+
+// FoundFragments of every hash of H (npgx_af_stats.n_found_frags) for a run on
+// one GPU, whose pass 2 looks at the groups the cut can keep alone: the total
+// goes to h_pinned[SLOT_CUT + CUT_TOTAL], valid after the caller's stream_wait.
+static void af_found_total_enqueue(npgx_af* af, const FoundOwed& o) {
+    Fills fills;
+    count_and_cut(af, o.A, o.nchunks, o.windows, o.nH, fills, SLOT_CUT, [] {});
+}
+
+// The first `keep` sorted FoundFragment keys (cand_sorted) and the G kept
+// hashes (the front of huniq) -> host_keys / host_H, through pinned_dl; waits
+// for the stream.
+static void download_keys(npgx_af* af, uint64_t keep, uint64_t G) {
+    hipStream_t st = af->stream;
+    af->host_keys.resize((size_t)keep);
+    af->host_H.resize((size_t)G);
+    uint64_t* pk = af->pinned_dl.ensure((size_t)(keep + G) * 8 + 8);
+    if (keep) NPGX_HIP(hipMemcpyAsync(pk, af->cand_sorted.p, (size_t)keep * 8, hipMemcpyDeviceToHost, st));
+    if (G) NPGX_HIP(hipMemcpyAsync(pk + keep, af->huniq.p, (size_t)G * 8, hipMemcpyDeviceToHost, st));
+    NPGX_HIP(stream_wait(st));
+    if (keep) memcpy(af->host_keys.data(), pk, (size_t)keep * 8);
+    if (G) memcpy(af->host_H.data(), pk + keep, (size_t)G * 8);
 }
 
 static void af_group_host(npgx_af* af, const std::vector<uint64_t>& keys, const std::vector<uint64_t>& Hh,
@@ -862,197 +959,245 @@ static void af_materialize(npgx_af* af);
 static void af_pending_used(npgx_af* af);
 static void af_found_pending(npgx_af* af);
 
-static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
-    static const bool hdbg = getenv("NPGX_AF_DEBUG") != nullptr;  // host phase times to stderr
-    const auto th0 = std::chrono::steady_clock::now();
-    auto hms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count(); };
-    double h_prep = 0, h_dl = 0;
-    NPGX_REQUIRE(ss->device == af->device, NPGX_ERR_ARG, "sequence set and finder on different devices");
-    NPGX_HIP(hipSetDevice(af->device));
-    hipStream_t st = af->stream;
-    const int k = af->opt.anchor_size;
-    // a deferred result nobody asked for is dropped; only the used hashes it
-    // owes the set (no npgx_af_clear_used since) are added, never its fragments
-    if (af->pending) {
-        if (af->pending_used) af_pending_used(af);
-        af->pending = false;
-    }
-    af->found_pending = false;  // (nor is its FoundFragment total owed any longer)
-    af->timer.reset();
-    af->has_result = false;
-    npgx_af_stats& S = af->stats;
-    memset(&S, 0, sizeof(S));
-
-    // --- Bloom sizing (BloomTG::initialize_bloom AnchorFinder.cpp:120-131)
-    uint64_t members = estimate_length(ss);
-    if (k * 2 < 64) members = std::min<uint64_t>(members, 1ull << (2 * k));
-    const double fp = double(af->opt.anchor_fp_x1e4) / 10000.0;  // Decimal::to_d
-    const int64_t m = optimal_bits(members, fp);
-    NPGX_REQUIRE(m > 0, NPGX_ERR_RANGE, "Bloom filter size overflows the reference's int");
-    const int kb = optimal_hashes(members, (uint64_t)m);
-    NPGX_REQUIRE(kb <= MAX_KB, NPGX_ERR_RANGE, "too many Bloom hash functions");
-    AfArgs A;
-    memset(&A, 0, sizeof(A));
-    if (!af->explicit_params.empty()) {
-        NPGX_REQUIRE((int)af->explicit_params.size() >= kb, NPGX_ERR_ARG,
-                     "explicit Bloom parameter vector shorter than the hash count");
-        for (int i = 0; i < kb; i++) A.params[i] = af->explicit_params[i];
-    } else {
-        glibc_rand(af->opt.bloom_seed, kb, A.params);
-    }
-    S.members = (int64_t)members;
-    S.bloom_bits = m;
-    S.bloom_hashes = kb;
-    for (int i = 0; i < kb; i++) S.bloom_params[i] = A.params[i];
-
-    // --- eligible sequences (size >= k) are a prefix of the rank order
+// One run of the finder as the steps af_run pipes (comm == null: one GPU).
+// Every step says what it enqueues on the stream and what it waits for.
+struct AfRun {
+    npgx_af* const af;
+    const npgx_seqset* const ss;
+    const npgx_comm* const comm;
+    const hipStream_t st;
+    npgx_af_stats& S;
+    uint64_t* const hp;  // af->h_pinned (Slot)
+    const int k;
+    const std::chrono::steady_clock::time_point th0 = std::chrono::steady_clock::now();
+    double h_prep = 0, h_dl = 0;  // host phase times (NPGX_AF_DEBUG)
+    // the Bloom plan
+    uint64_t members = 0;
+    int64_t m = 0;
+    int kb = 0;
+    // the eligible sequences (size >= k), a prefix of the rank order, and their windows
     int32_t R = 0;
-    while (R < ss->n && (int64_t)ss->data[ss->by_rank[R]].size() >= k) R++;
-    std::vector<SeqMeta> meta(R > 0 ? R : 1);
+    std::vector<SeqMeta> meta;
     uint64_t order = 0;
     int64_t n_windows = 0;
-    for (int32_t r = 0; r < R; r++) {
-        const int64_t size = (int64_t)ss->data[ss->by_rank[r]].size();
-        meta[r] = SeqMeta{size, ss->word_off[r], ss->n_off[r], order};
-        order += (uint64_t)size;
-        n_windows += size - k + 1;
-    }
-    // the window layout depends only on the sequence set and k: built and
-    // uploaded once per (set, k) and reused by later runs of this handle
-    const bool same_layout = af->layout_k == k && af->layout_meta.size() == meta.size() &&
-                             memcmp(af->layout_meta.data(), meta.data(), meta.size() * sizeof(SeqMeta)) == 0;
-    std::vector<Chunk>& chunks = af->layout_chunks;
-    if (!same_layout) {
-        chunks.clear();
-        for (int32_t r = 0; r < R; r++)
-            for (int64_t p = 0; p < meta[r].size - k + 1; p += WG) chunks.push_back(Chunk{r, 0, p});
-    }
-    // window orders are 32-bit (first[] holds one per Bloom bit): a run over
-    // more bases is refused, never wrapped.  NPGX_AF_MAX_BASES lowers the
-    // limit (tests exercise the refusal without a 4 Gbp input).
-    static const uint64_t max_bases = [] {
-        const char* e = getenv("NPGX_AF_MAX_BASES");
-        const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
-        return v > 0 && v < 0xFFFFFFFEull ? v : 0xFFFFFFFEull;
-    }();
-    NPGX_REQUIRE(order < max_bases, NPGX_ERR_RANGE, "more than 2^32-2 bases in one run (32-bit window orders)");
-    S.n_windows = n_windows;
-    S.n_used = (int64_t)af->used.size();
+    bool same_layout = false;
+    // this rank scans the contiguous chunk range [c0, c1) of nchunks_all
+    int world = 1, rank = 0;
+    int64_t nchunks_all = 0, c0 = 0, c1 = 0, nchunks = 0, local_windows = 0;
+    bool run_local = false;  // ranks without windows still join every collective
+    AfArgs A;
+    // bit arrays (uint32 words, W each): P (bits set before this epoch) | Pn
+    // (through this one) | this rank's bits | P0 (the lower ranks' bits; sharded)
+    int64_t w64 = 0, W = 0;
+    uint32_t *P = nullptr, *Pn = nullptr, *mine = nullptr, *P0 = nullptr;
+    unsigned long long *bfirst = nullptr, *blast = nullptr;  // sharded: counters[4..5], counters[6]
+    Fills fills;  // resets waiting for the next k_fill_multi launch
+    int key_bits = 0;
+    int64_t n_raw = 0, nH = 0;
+    uint64_t n_keys = 0, keep = 0, G = 0;
+    std::vector<int64_t> rc;  // gather_u64: every rank's count
 
-    // persistent used hashes on the device
-    if (af->used_dirty) {
-        af->d_used.ensure(af->used.size());
-        if (!af->used.empty())
-            NPGX_HIP(hipMemcpyAsync(af->d_used.p, af->used.data(), af->used.size() * 8,
-                                    hipMemcpyHostToDevice, st));
-        af->used_dirty = false;
+    AfRun(npgx_af* af_, const npgx_seqset* ss_, const npgx_comm* comm_)
+        : af(af_), ss(ss_), comm(comm_), st(af_->stream), S(af_->stats), hp(af_->h_pinned),
+          k(af_->opt.anchor_size) {}
+
+    double hms() const {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
     }
-    const int64_t nchunks_all = (int64_t)chunks.size();
-    // sharded run: this rank scans the contiguous chunk range [c0, c1)
-    const int world = comm ? comm->world : 1;
-    const int rank = comm ? comm->rank : 0;
-    const int64_t c0 = nchunks_all * rank / world, c1 = nchunks_all * (rank + 1) / world;
-    const int64_t nchunks = c1 - c0;
-    if (comm) NPGX_REQUIRE(n_windows < (1ll << 31), NPGX_ERR_RANGE,
-                           "sharded run: FoundFragment counts must fit int32");
-    if (!same_layout || af->layout_c0 != c0 || af->layout_c1 != c1) {
-        int64_t lw = 0;
-        for (int64_t c = c0; c < c1; c++) lw += std::min<int64_t>(WG, meta[chunks[c].seq].size - k + 1 - chunks[c].pos);
-        af->layout_local = lw;
-        af->layout_c0 = c0;
-        af->layout_c1 = c1;
+    dim3 grid() const { return dim3((unsigned)std::max<int64_t>(nchunks, 1)); }
+
+    // A deferred result nobody asked for is dropped: only the used hashes it
+    // owes the set (no npgx_af_clear_used since) are added, never its
+    // fragments, and its FoundFragment total is owed no longer.  Adding them
+    // downloads the old keys (a wait).
+    void drop_pending() {
+        if (af->pending && af->pending_used) af_pending_used(af);
+        af->pending = false;
+        af->found_pending = false;
+        af->deferred = Pending{};
+        af->found_owed = FoundOwed{};
+        af->timer.reset();
+        af->has_result = false;
+        memset(&S, 0, sizeof(S));
     }
-    const int64_t local_windows = af->layout_local;
-    if (nchunks_all == 0) {
+
+    // Bloom sizing (BloomTG::initialize_bloom AnchorFinder.cpp:120-131) and the hash parameters; host only
+    void size_bloom() {
+        members = estimate_length(ss);
+        if (k * 2 < 64) members = std::min<uint64_t>(members, 1ull << (2 * k));
+        const double fp = double(af->opt.anchor_fp_x1e4) / 10000.0;  // Decimal::to_d
+        m = optimal_bits(members, fp);
+        NPGX_REQUIRE(m > 0, NPGX_ERR_RANGE, "Bloom filter size overflows the reference's int");
+        kb = optimal_hashes(members, (uint64_t)m);
+        NPGX_REQUIRE(kb <= MAX_KB, NPGX_ERR_RANGE, "too many Bloom hash functions");
+        memset(&A, 0, sizeof(A));
+        if (!af->explicit_params.empty()) {
+            NPGX_REQUIRE((int)af->explicit_params.size() >= kb, NPGX_ERR_ARG,
+                         "explicit Bloom parameter vector shorter than the hash count");
+            for (int i = 0; i < kb; i++) A.params[i] = af->explicit_params[i];
+        } else {
+            glibc_rand(af->opt.bloom_seed, kb, A.params);
+        }
+        S.members = (int64_t)members;
+        S.bloom_bits = m;
+        S.bloom_hashes = kb;
+        for (int i = 0; i < kb; i++) S.bloom_params[i] = A.params[i];
+    }
+
+    // The eligible sequences, their chunks of WG windows (af->layout_chunks,
+    // rebuilt when the set or k changed) and this rank's range of them; host
+    // only, but for the upload of a changed used-hash set (enqueued)
+    void layout() {
+        while (R < ss->n && (int64_t)ss->data[ss->by_rank[R]].size() >= k) R++;
+        meta.resize(R > 0 ? R : 1);
+        for (int32_t r = 0; r < R; r++) {
+            const int64_t size = (int64_t)ss->data[ss->by_rank[r]].size();
+            meta[r] = SeqMeta{size, ss->word_off[r], ss->n_off[r], order};
+            order += (uint64_t)size;
+            n_windows += size - k + 1;
+        }
+        // the window layout depends only on the sequence set and k: built and
+        // uploaded once per (set, k) and reused by later runs of this handle
+        same_layout = af->layout_k == k && af->layout_meta.size() == meta.size() &&
+                      memcmp(af->layout_meta.data(), meta.data(), meta.size() * sizeof(SeqMeta)) == 0;
+        std::vector<Chunk>& chunks = af->layout_chunks;
+        if (!same_layout) {
+            chunks.clear();
+            for (int32_t r = 0; r < R; r++)
+                for (int64_t p = 0; p < meta[r].size - k + 1; p += WG) chunks.push_back(Chunk{r, 0, p});
+        }
+        // window orders are 32-bit (first[] holds one per Bloom bit): a run over
+        // more bases is refused, never wrapped.  NPGX_AF_MAX_BASES lowers the
+        // limit (tests exercise the refusal without a 4 Gbp input).
+        static const uint64_t max_bases = [] {
+            const char* e = getenv("NPGX_AF_MAX_BASES");
+            const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+            return v > 0 && v < 0xFFFFFFFEull ? v : 0xFFFFFFFEull;
+        }();
+        NPGX_REQUIRE(order < max_bases, NPGX_ERR_RANGE, "more than 2^32-2 bases in one run (32-bit window orders)");
+        S.n_windows = n_windows;
+        S.n_used = (int64_t)af->used.size();
+        // persistent used hashes on the device
+        if (af->used_dirty) {
+            af->d_used.ensure(af->used.size());
+            if (!af->used.empty())
+                NPGX_HIP(hipMemcpyAsync(af->d_used.p, af->used.data(), af->used.size() * 8,
+                                        hipMemcpyHostToDevice, st));
+            af->used_dirty = false;
+        }
+        nchunks_all = (int64_t)chunks.size();
+        world = comm ? comm->world : 1;
+        rank = comm ? comm->rank : 0;
+        c0 = nchunks_all * rank / world;
+        c1 = nchunks_all * (rank + 1) / world;
+        nchunks = c1 - c0;
+        run_local = nchunks > 0;
+        if (comm) NPGX_REQUIRE(n_windows < (1ll << 31), NPGX_ERR_RANGE,
+                               "sharded run: FoundFragment counts must fit int32");
+        if (!same_layout || af->layout_c0 != c0 || af->layout_c1 != c1) {
+            int64_t lw = 0;
+            for (int64_t c = c0; c < c1; c++)
+                lw += std::min<int64_t>(WG, meta[chunks[c].seq].size - k + 1 - chunks[c].pos);
+            af->layout_local = lw;
+            af->layout_c0 = c0;
+            af->layout_c1 = c1;
+        }
+        local_windows = af->layout_local;
+    }
+
+    // no sequence holds a window: the empty result; host only
+    void empty_result() {
         af->r_block_start.assign(1, 0);
         af->r_seq.clear();
         af->r_min.clear();
         af->r_max.clear();
         af->r_ori.clear();
         af->has_result = true;
-        return;
     }
-    if (!same_layout) {
+
+    // a changed layout goes up (d_meta, d_chunks) and is waited for: the host vectors are pageable
+    void upload_layout() {
+        if (same_layout) return;
+        const std::vector<Chunk>& chunks = af->layout_chunks;
         af->d_meta.ensure(meta.size());
         af->d_chunks.ensure(chunks.size());
         NPGX_HIP(hipMemcpyAsync(af->d_meta.p, meta.data(), meta.size() * sizeof(SeqMeta),
                                 hipMemcpyHostToDevice, st));
         NPGX_HIP(hipMemcpyAsync(af->d_chunks.p, chunks.data(), chunks.size() * sizeof(Chunk),
                                 hipMemcpyHostToDevice, st));
-        NPGX_HIP(stream_wait(st));  // the host vectors are pageable and local
+        NPGX_HIP(stream_wait(st));
         af->layout_meta = meta;
         af->layout_k = k;
         af->layout_n = (int64_t)chunks.size();
     }
 
-    A.meta = af->d_meta.p;
-    A.chunks = af->d_chunks.p + c0;
-    A.words = ss->words.p;
-    A.nmask = ss->nmask.p;
-    A.used = af->d_used.p;
-    A.n_used = (int64_t)af->used.size();
-    A.k = k;
-    A.kb = kb;
-    A.kmask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-    A.nbits_mask = (k == 32) ? 0xFFFFFFFFu : ((1u << k) - 1);
-    A.m = (uint32_t)m;
-    A.mmagic = ~0ull / (uint64_t)m;
-    A.similar = af->opt.anchor_similar ? 1 : 0;
-
-    const dim3 grid((unsigned)std::max<int64_t>(nchunks, 1)), block(WG);
-    h_prep = hms();
-    const bool run_local = nchunks > 0;  // ranks without windows still join every collective
-    uint64_t* hp = af->h_pinned;
-
-    // --- pass 1: Bloom first-setter + found/collect
-    af->first.ensure((size_t)m);
-    af->counters.ensure(8);  // [0] collected, [1] unique, [4..6] sharded boundary
-    Fills fills;  // the run's resets, one launch (k_fill_multi)
-    fills.add(af->counters.p, 4 * sizeof(unsigned long long), 0u);
-    af->hraw.ensure((size_t)local_windows + 1);
-    // found_collect appends into nseg segments (global chunk index mod nseg),
-    // each with room for all windows of its chunks
-    A.nseg = (int32_t)std::max<int64_t>(1, std::min<int64_t>(256, nchunks));
-    A.seg_cap = (nchunks + A.nseg - 1) / A.nseg * WG;
-    A.chunk_base = 0;
-    af->hseg.ensure((size_t)(A.nseg * A.seg_cap));
-    af->segctr.ensure((size_t)A.nseg * 16);
-    fills.add(af->segctr.p, (int64_t)A.nseg * 16 * 8, 0u);
-    if (kb <= FKB && nchunks > 0) {  // every byte is written by k_bloom_first_f before it is read
-        af->wmask.ensure((size_t)nchunks * WG);
-        A.wmask = af->wmask.p;
+    // A (but the Bloom parameters, set by size_bloom) and the buffers pass 1 writes; host only
+    void kernel_args() {
+        A.meta = af->d_meta.p;
+        A.chunks = af->d_chunks.p + c0;
+        A.words = ss->words.p;
+        A.nmask = ss->nmask.p;
+        A.used = af->d_used.p;
+        A.n_used = (int64_t)af->used.size();
+        A.k = k;
+        A.kb = kb;
+        A.kmask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
+        A.nbits_mask = (k == 32) ? 0xFFFFFFFFu : ((1u << k) - 1);
+        A.m = (uint32_t)m;
+        A.mmagic = ~0ull / (uint64_t)m;
+        A.similar = af->opt.anchor_similar ? 1 : 0;
+        h_prep = hms();
+        af->first.ensure((size_t)m);
+        af->counters.ensure(8);
+        af->hraw.ensure((size_t)local_windows + 1);
+        // found_collect appends into nseg segments (global chunk index mod nseg),
+        // each with room for all windows of its chunks
+        A.nseg = (int32_t)std::max<int64_t>(1, std::min<int64_t>(256, nchunks));
+        A.seg_cap = (nchunks + A.nseg - 1) / A.nseg * WG;
+        A.chunk_base = 0;
+        af->hseg.ensure((size_t)(A.nseg * A.seg_cap));
+        af->segctr.ensure((size_t)A.nseg * 16);
+        if (kb <= FKB && nchunks > 0) {  // every byte is written by k_bloom_first_f before it is read
+            af->wmask.ensure((size_t)nchunks * WG);
+            A.wmask = af->wmask.p;
+        }
+        w64 = ((int64_t)m + 63) / 64;
+        W = 2 * w64;
+        af->bloom_bits.ensure((size_t)(4 * W));
+        P = af->bloom_bits.p;
+        Pn = P + W;
+        mine = P + 2 * W;
+        bfirst = comm ? af->counters.p + 4 : nullptr;
+        blast = comm ? af->counters.p + 6 : nullptr;
     }
-    size_t ti = 0;
-    // bit arrays (uint32 words, W each): P (bits set before this epoch) | Pn
-    // (through this one) | this rank's bits | P0 (the lower ranks' bits)
-    const int64_t w64 = ((int64_t)m + 63) / 64, W = 2 * w64;
-    af->bloom_bits.ensure((size_t)(4 * W));
-    uint32_t* P = af->bloom_bits.p;
-    uint32_t* Pn = P + W;
-    uint32_t* mine = P + 2 * W;
-    uint32_t* P0 = nullptr;
-    unsigned long long* bfirst = comm ? af->counters.p + 4 : nullptr;
-    unsigned long long* blast = comm ? af->counters.p + 6 : nullptr;
-    ti = af->timer.begin("bloom_first", st, local_windows * (0.375 + 8.0 * kb), local_windows);
-    fills.add(af->first.p, m * 4, 0xFFFFFFFFu);
-    if (comm) {
-        fills.add(af->counters.p + 4, 3 * 8, 0u);
-        fills.add(mine, W * 4, 0u);
-    } else {
-        fills.add(P, 2 * W * 4, 0u);
+
+    // pass 1's resets in one k_fill_multi launch: the counters, first[], the bit arrays
+    void reset_pass1() {
+        fills.add(af->counters.p, 4 * sizeof(unsigned long long), 0u);
+        fills.add(af->segctr.p, (int64_t)A.nseg * 16 * 8, 0u);
+        const size_t ti = af->timer.begin("bloom_first", st, local_windows * (0.375 + 8.0 * kb), local_windows);
+        fills.add(af->first.p, m * 4, 0xFFFFFFFFu);
+        if (comm) {
+            fills.add(af->counters.p + 4, 3 * 8, 0u);
+            fills.add(mine, W * 4, 0u);
+        } else {
+            fills.add(P, 2 * W * 4, 0u);
+        }
+        fills.launch(st);
+        NPGX_HIP(hipGetLastError());
+        af->timer.end(ti, st);
     }
-    fills.launch(st);
-    NPGX_HIP(hipGetLastError());
-    af->timer.end(ti, st);
-    if (comm) {
-        // exchange 1: every rank's Bloom bit array (m / 8 bytes); this rank
-        // keeps the OR of the lower ranks' (P0), whose windows all precede
-        // its own: a window here is found iff each of its bits is in P0 or was
-        // set by an earlier window of this rank (first[] over the bits outside
-        // P0) -- the reference's sequential test exactly.  P and Pn start at P0.
+
+    // Exchange 1 (sharded): every rank's Bloom bit array (m / 8 bytes); this
+    // rank keeps the OR of the lower ranks' (P0), whose windows all precede
+    // its own: a window here is found iff each of its bits is in P0 or was
+    // set by an earlier window of this rank (first[] over the bits outside
+    // P0) -- the reference's sequential test exactly.  P and Pn start at P0.
+    // Enqueues k_bloom_bits, waits, gathers, enqueues the OR and the two copies.
+    void exchange_bits() {
         P0 = P + 3 * W;
-        ti = af->timer.begin("bloom_bits_exchange", st, (double)m / 8 * world, m);
-        if (run_local) hipLaunchKernelGGL(k_bloom_bits, grid, block, 0, st, A, mine);
+        const size_t ti = af->timer.begin("bloom_bits_exchange", st, (double)m / 8 * world, m);
+        if (run_local) hipLaunchKernelGGL(k_bloom_bits, grid(), dim3(WG), 0, st, A, mine);
         NPGX_HIP(hipGetLastError());
         std::vector<int64_t> cnt(world, w64);
         af->gathered.grow((size_t)(w64 * world));
@@ -1066,7 +1211,40 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
         NPGX_HIP(hipMemcpyAsync(Pn, P0, (size_t)W * 4, hipMemcpyDeviceToDevice, st));
         af->timer.end(ti, st);
     }
-    if (af->opt.bloom_epochs != 1 && run_local) {
+
+    AfArgs epoch_args(int64_t e0) const {  // A over the chunks from this rank's e0-th on
+        AfArgs E = A;
+        E.chunks = A.chunks + e0;
+        E.chunk_base = e0;
+        return E;
+    }
+    // k_bloom_first_f over the first nblk chunks of E
+    void launch_bloom_first(const AfArgs& E, int64_t nblk) {
+        hipLaunchKernelGGL(k_bloom_first_f, dim3((unsigned)nblk), dim3(WG), 0, st, E, af->first.p, P);
+        NPGX_HIP(hipGetLastError());
+    }
+    // k_found_collect_f over the first nblk chunks of E.  Pw: where the epoch's
+    // new bits go (null: no epoch follows); first / last: the epoch holds the
+    // range's first / last window (the sharded boundary reports)
+    void launch_found_collect(const AfArgs& E, int64_t nblk, uint32_t* Pw, bool first, bool last) {
+        hipLaunchKernelGGL(k_found_collect_f, dim3((unsigned)nblk), dim3(WG), 0, st, E, af->first.p, P, Pw,
+                           af->hseg.p, af->segctr.p, P0, first ? bfirst : nullptr, last ? blast : nullptr);
+        NPGX_HIP(hipGetLastError());
+    }
+
+    // Pass 1 over this rank's chunks, Bloom first-setter + found/collect:
+    // fused epochs, unfused epochs or the single pass; enqueues only
+    void bloom_pass() {
+        if (!run_local) return;
+        if (af->opt.bloom_epochs == 1) {
+            size_t ti = af->timer.begin("bloom_first", st, 0.0, 0);
+            launch_bloom_first(A, nchunks);
+            af->timer.end(ti, st);
+            ti = af->timer.begin("found_collect", st, local_windows * (0.375 + 4.0 * kb), local_windows);
+            launch_found_collect(A, nchunks, nullptr, true, true);
+            af->timer.end(ti, st);
+            return;
+        }
         // epochs of consecutive chunks (SeqMeta order); bits set by earlier
         // epochs (or lower ranks) skip the atomics and the first[] reads.
         // Automatic count: one epoch per 2 M windows, at most 24 (each epoch
@@ -1083,128 +1261,114 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
             1, (int64_t)std::ceil(double(nchunks) / std::max(1, af->opt.bloom_epochs > 0 ? af->opt.bloom_epochs
                                                                                           : auto_epochs)));
         static const bool fuse_env = !(getenv("NPGX_AF_EPOCH_FUSE") && getenv("NPGX_AF_EPOCH_FUSE")[0] == '0');
-        const bool fuse = fuse_env && Pw == P && af->timer.level < 2;  // (NPGX_TIMERS=2 times each pass)
-        auto epoch_args = [&](int64_t e0) {
-            AfArgs E = A;
-            E.chunks = A.chunks + e0;
-            E.chunk_base = e0;
-            return E;
-        };
-        if (fuse) {  // k_bloom_epoch_f: collect of epoch e with the first-setter pass of e + 1
-            hipLaunchKernelGGL(k_bloom_first_f, dim3((unsigned)std::min(per, nchunks)), block, 0, st, epoch_args(0),
-                               af->first.p, P);
-            for (int64_t e0 = 0; e0 < nchunks; e0 += per) {
-                const int64_t ne = std::min(per, nchunks - e0), e1 = e0 + ne;
-                if (e1 < nchunks) {
-                    const int64_t nn = std::min(per, nchunks - e1);
-                    hipLaunchKernelGGL(k_bloom_epoch_f, dim3((unsigned)(ne + nn)), block, 0, st, epoch_args(e0),
-                                       epoch_args(e1), ne, af->first.p, P, af->hseg.p, af->segctr.p, P0,
-                                       e0 == 0 ? bfirst : nullptr);
-                } else {
-                    hipLaunchKernelGGL(k_found_collect_f, dim3((unsigned)ne), block, 0, st, epoch_args(e0), af->first.p,
-                                       P, nullptr, af->hseg.p, af->segctr.p, P0, e0 == 0 ? bfirst : nullptr, blast);
-                }
-                NPGX_HIP(hipGetLastError());
+        if (fuse_env && Pw == P && af->timer.level < 2) fused_epochs(per);  // (NPGX_TIMERS=2 times each pass)
+        else unfused_epochs(per, Pw);
+    }
+    // k_bloom_epoch_f: the collect of epoch e with the first-setter pass of e + 1, untimed
+    void fused_epochs(int64_t per) {
+        launch_bloom_first(epoch_args(0), std::min(per, nchunks));
+        for (int64_t e0 = 0; e0 < nchunks; e0 += per) {
+            const int64_t ne = std::min(per, nchunks - e0), e1 = e0 + ne;
+            if (e1 == nchunks) {
+                launch_found_collect(epoch_args(e0), ne, nullptr, e0 == 0, true);
+                break;
             }
+            const int64_t nn = std::min(per, nchunks - e1);
+            hipLaunchKernelGGL(k_bloom_epoch_f, dim3((unsigned)(ne + nn)), dim3(WG), 0, st, epoch_args(e0),
+                               epoch_args(e1), ne, af->first.p, P, af->hseg.p, af->segctr.p, P0,
+                               e0 == 0 ? bfirst : nullptr);
+            NPGX_HIP(hipGetLastError());
         }
-        for (int64_t e0 = 0; e0 < nchunks && !fuse; e0 += per) {
+    }
+    // two launches an epoch and, without the window masks, the copy of Pn to P
+    void unfused_epochs(int64_t per, uint32_t* Pw) {
+        for (int64_t e0 = 0; e0 < nchunks; e0 += per) {
             const int64_t ne = std::min(per, nchunks - e0);
             const AfArgs E = epoch_args(e0);
-            const dim3 eg((unsigned)ne);
-            ti = af->timer.begin("bloom_first", st, 0.0, 0);
-            hipLaunchKernelGGL(k_bloom_first_f, eg, block, 0, st, E, af->first.p, P);
-            NPGX_HIP(hipGetLastError());
+            size_t ti = af->timer.begin("bloom_first", st, 0.0, 0);
+            launch_bloom_first(E, ne);
             af->timer.end(ti, st);
             ti = af->timer.begin("found_collect", st, local_windows * (0.375 + 4.0 * kb) * double(ne) / nchunks, 0);
             const bool more = e0 + ne < nchunks;
-            hipLaunchKernelGGL(k_found_collect_f, eg, block, 0, st, E, af->first.p, P, more ? Pw : nullptr,
-                               af->hseg.p, af->segctr.p, P0, e0 == 0 ? bfirst : nullptr,
-                               more ? nullptr : blast);
-            NPGX_HIP(hipGetLastError());
+            launch_found_collect(E, ne, more ? Pw : nullptr, e0 == 0, !more);
             af->timer.end(ti, st);
             if (more && Pw != P) NPGX_HIP(hipMemcpyAsync(P, Pn, (size_t)W * 4, hipMemcpyDeviceToDevice, st));
         }
-    } else if (run_local) {
-        ti = af->timer.begin("bloom_first", st, 0.0, 0);
-        hipLaunchKernelGGL(k_bloom_first_f, grid, block, 0, st, A, af->first.p, P);
-        NPGX_HIP(hipGetLastError());
-        af->timer.end(ti, st);
-        ti = af->timer.begin("found_collect", st, local_windows * (0.375 + 4.0 * kb), local_windows);
-        hipLaunchKernelGGL(k_found_collect_f, grid, block, 0, st, A, af->first.p, P, nullptr, af->hseg.p,
-                           af->segctr.p, P0, bfirst, blast);
-        NPGX_HIP(hipGetLastError());
-        af->timer.end(ti, st);
     }
-    if (run_local) {  // the collected hashes packed into hraw, their count into counters[0]
-        ti = af->timer.begin("collect_pack", st, 0.0, 0);
+
+    // the collected hashes packed into hraw, their count into counters[0]; enqueues k_seg_compact
+    void pack_collected() {
+        if (!run_local) return;
+        const size_t ti = af->timer.begin("collect_pack", st, 0.0, 0);
         hipLaunchKernelGGL(k_seg_compact, dim3((unsigned)A.nseg), dim3(256), 0, st, af->hseg.p, af->segctr.p,
                            A.nseg, A.seg_cap, af->hraw.p, af->counters.p);
         NPGX_HIP(hipGetLastError());
         af->timer.end(ti, st);
     }
-    if (comm) {
-        NPGX_HIP(hipMemcpyAsync(hp, af->counters.p, 8 * 8, hipMemcpyDeviceToHost, st));
+
+    // Exchange 2 (sharded): every rank's last window (order, found): the similar
+    // rule (AnchorFinder.cpp:185-192) for this range's first window, which
+    // pass 1 reported instead of collecting.  Downloads the counters (a wait);
+    // a first window collected after all is appended to hraw (another wait).
+    void exchange_boundary() {
+        NPGX_HIP(hipMemcpyAsync(hp + SLOT_BOUNDARY, af->counters.p, 8 * 8, hipMemcpyDeviceToHost, st));
         NPGX_HIP(stream_wait(st));
-        // exchange 2: every rank's last window (order, found): the similar
-        // rule (AnchorFinder.cpp:185-192) for this range's first window
         int64_t mine_last = -1;
         uint64_t first_order = 0;
         bool pred_elsewhere = false;
         if (run_local) {
-            const Chunk& cf = chunks[c0];
-            const Chunk& cl = chunks[c1 - 1];
+            const Chunk& cf = af->layout_chunks[c0];
+            const Chunk& cl = af->layout_chunks[c1 - 1];
             const int64_t last_p = std::min<int64_t>(WG, meta[cl.seq].size - k + 1 - cl.pos) - 1 + cl.pos;
-            mine_last = (int64_t)(((meta[cl.seq].order_off + (uint64_t)last_p) << 1) | (hp[6] & 1ull));
+            mine_last = (int64_t)(((meta[cl.seq].order_off + (uint64_t)last_p) << 1) | (hp[SLOT_LAST_FOUND] & 1ull));
             first_order = meta[cf.seq].order_off + (uint64_t)cf.pos;
             pred_elsewhere = cf.pos > 0;
         }
         std::vector<int64_t> lasts(world);
         comm_check(comm->allgather_i64(comm->user, mine_last, lasts.data()), "allgather(boundary windows)");
-        if (pred_elsewhere && (hp[4] & 1ull)) {
-            bool prev = false, seen = false;
-            for (int q = 0; q < world; q++)
-                if (lasts[q] >= 0 && (uint64_t)(lasts[q] >> 1) + 1 == first_order) {
-                    prev = (lasts[q] & 1) != 0;
-                    seen = true;
-                }
-            NPGX_REQUIRE(seen, NPGX_ERR_STATE, "sharded run: the boundary window's rank is missing");
-            if (!(af->opt.anchor_similar && prev)) {  // collected after all: appended
-                const uint64_t h0 = hp[5];
-                const uint64_t n1 = hp[0] + 1;
-                NPGX_HIP(hipMemcpyAsync(af->hraw.p + hp[0], &h0, 8, hipMemcpyHostToDevice, st));
-                NPGX_HIP(hipMemcpyAsync(af->counters.p, &n1, 8, hipMemcpyHostToDevice, st));
-                NPGX_HIP(stream_wait(st));
+        if (!pred_elsewhere || !(hp[SLOT_FIRST_FOUND] & 1ull)) return;
+        bool prev = false, seen = false;
+        for (int q = 0; q < world; q++)
+            if (lasts[q] >= 0 && (uint64_t)(lasts[q] >> 1) + 1 == first_order) {
+                prev = (lasts[q] & 1) != 0;
+                seen = true;
             }
-        }
+        NPGX_REQUIRE(seen, NPGX_ERR_STATE, "sharded run: the boundary window's rank is missing");
+        if (af->opt.anchor_similar && prev) return;
+        const uint64_t h0 = hp[SLOT_FIRST_HASH];
+        const uint64_t n1 = hp[SLOT_N_RAW] + 1;
+        NPGX_HIP(hipMemcpyAsync(af->hraw.p + hp[SLOT_N_RAW], &h0, 8, hipMemcpyHostToDevice, st));
+        NPGX_HIP(hipMemcpyAsync(af->counters.p, &n1, 8, hipMemcpyHostToDevice, st));
+        NPGX_HIP(stream_wait(st));
     }
-    NPGX_HIP(hipMemcpyAsync(hp, af->counters.p, 8, hipMemcpyDeviceToHost, st));
-    NPGX_HIP(stream_wait(st));
-    const int64_t n_raw = (int64_t)hp[0];
-    S.n_collected_raw = n_raw;
 
-    // --- bloomtg_postprocess (AnchorFinder.cpp:213-218): sort + unique
-    const unsigned h_end_bit = (unsigned)std::min(64, 2 * k);
-    auto sort_unique = [&](const uint64_t* in, int64_t n) -> int64_t {
+    // bloomtg_postprocess (AnchorFinder.cpp:213-218): n sorted, the unique ones
+    // to huniq; their count is waited for
+    int64_t sort_unique(const uint64_t* in, int64_t n) {
         if (n <= 0) return 0;
         af->hsorted.ensure((size_t)n);
         af->huniq.ensure((size_t)n);
-        size_t b1 = 0, b2 = 0;
-        NPGX_HIP(rocprim::radix_sort_keys(nullptr, b1, in, af->hsorted.p, (size_t)n, 0u, h_end_bit, st));
-        NPGX_HIP(rocprim::unique(nullptr, b2, af->hsorted.p, af->huniq.p, af->counters.p + 1,
-                                 (size_t)n, rocprim::equal_to<uint64_t>(), st));
-        af->ensure_temp(std::max(b1, b2));
-        size_t t = af->timer.begin("sort_unique_H", st, n * 8.0 * 4, n);
-        NPGX_HIP(rocprim::radix_sort_keys(af->temp.p, b1, in, af->hsorted.p, (size_t)n, 0u, h_end_bit, st));
-        NPGX_HIP(rocprim::unique(af->temp.p, b2, af->hsorted.p, af->huniq.p, af->counters.p + 1,
-                                 (size_t)n, rocprim::equal_to<uint64_t>(), st));
-        af->timer.end(t, st);
-        NPGX_HIP(hipMemcpyAsync(hp, af->counters.p + 1, 8, hipMemcpyDeviceToHost, st));
+        const unsigned end_bit = (unsigned)std::min(64, 2 * k);
+        auto sort = [&](void* t, size_t& b) {
+            return rocprim::radix_sort_keys(t, b, in, af->hsorted.p, (size_t)n, 0u, end_bit, st);
+        };
+        auto unique = [&](void* t, size_t& b) {
+            return rocprim::unique(t, b, af->hsorted.p, af->huniq.p, af->counters.p + 1, (size_t)n,
+                                   rocprim::equal_to<uint64_t>(), st);
+        };
+        size_t b1 = prim_temp(af, sort), b2 = prim_temp(af, unique);  // (temp: the larger of the two)
+        const size_t ti = af->timer.begin("sort_unique_H", st, n * 8.0 * 4, n);
+        NPGX_HIP(sort((void*)af->temp.p, b1));
+        NPGX_HIP(unique((void*)af->temp.p, b2));
+        af->timer.end(ti, st);
+        NPGX_HIP(hipMemcpyAsync(hp + SLOT_N_UNIQUE, af->counters.p + 1, 8, hipMemcpyDeviceToHost, st));
         NPGX_HIP(stream_wait(st));
-        return (int64_t)hp[0];
-    };
-    std::vector<int64_t> rc(world);
-    // all-gather of this rank's n values from `src` into af->gathered; returns the total
-    auto gather_u64 = [&](const uint64_t* src, int64_t n, const char* what) -> int64_t {
+        return (int64_t)hp[SLOT_N_UNIQUE];
+    }
+    // all-gather of this rank's n values from `src` into af->gathered (a wait
+    // before the device buffers go to the callback); returns the total
+    int64_t gather_u64(const uint64_t* src, int64_t n, const char* what) {
+        rc.resize(world);
         comm_check(comm->allgather_i64(comm->user, n, rc.data()), what);
         int64_t tot = 0;
         for (int64_t v : rc) tot += v;
@@ -1212,36 +1376,42 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
         NPGX_HIP(stream_wait(st));
         if (tot > 0) comm_check(comm->allgatherv_u64(comm->user, src, rc.data(), af->gathered.p), what);
         return tot;
-    };
-    int64_t nH = sort_unique(af->hraw.p, n_raw);
-    if (comm) {
-        // exchange 2: every rank's unique collected hashes -> the global H
-        const int64_t tot = gather_u64(af->huniq.p, nH, "allgatherv(collected hashes)");
-        nH = sort_unique(af->gathered.p, tot);
     }
-    S.n_collected = nH;
+    // The count pass 1 collected (a wait), then H = its sorted unique hashes
+    // in huniq; sharded, exchange 3 gathers every rank's and sorts them again
+    void unique_hashes() {
+        NPGX_HIP(hipMemcpyAsync(hp + SLOT_N_RAW, af->counters.p, 8, hipMemcpyDeviceToHost, st));
+        NPGX_HIP(stream_wait(st));
+        n_raw = (int64_t)hp[SLOT_N_RAW];
+        S.n_collected_raw = n_raw;
+        nH = sort_unique(af->hraw.p, n_raw);
+        if (comm) {
+            const int64_t tot = gather_u64(af->huniq.p, nH, "allgatherv(collected hashes)");  // (may move gathered)
+            nH = sort_unique(af->gathered.p, tot);
+        }
+        S.n_collected = nH;
+        af->host_keys.clear();
+        af->host_H.clear();
+        key_bits = bits_for(2ull * order);
+    }
 
-    std::vector<uint64_t>& keys = af->host_keys;
-    std::vector<uint64_t>& Hh = af->host_H;
-    keys.clear();
-    Hh.clear();
-    uint64_t G = 0;
-    int key_bits = bits_for(2ull * order);
-    if (nH > 0 && !comm) {
-        // --- pass 2 on one GPU: the windows of the L smallest hashes of H
-        // (k_ff_collect), sorted, then the cut: the first keep keys, and
-        // G = the group of the last of them + 1.  The same (G, keep) as the
-        // counting path below: the group holding element max_frag - 1 is the
-        // last one starting before max_frag; the groups below L are complete
-        // in the buffer; and with fewer than max_frag keys L = nH (otherwise
-        // keys >= L = max_frag + 1).  The keys are distinct, so the sorted
-        // order does not depend on the order of the appends.
+    // Pass 2 on one GPU: the windows of the L smallest hashes of H
+    // (k_ff_collect), sorted, then the cut: the first keep keys, and
+    // G = the group of the last of them + 1.  The same (G, keep) as the
+    // counting path (keys_sharded): the group holding element max_frag - 1 is
+    // the last one starting before max_frag; the groups below L are complete
+    // in the buffer; and with fewer than max_frag keys L = nH (otherwise
+    // keys >= L = max_frag + 1).  The keys are distinct, so the sorted
+    // order does not depend on the order of the appends.
+    // Waits for the key count; the sort and the download of the last kept key
+    // (SLOT_LAST_KEY) are left enqueued.
+    void keys_one_gpu() {
         const uint64_t max_frag = (uint64_t)af->opt.max_anchor_fragments;
         const int64_t L = (int64_t)std::min<uint64_t>((uint64_t)nH, max_frag + 1);
         const int idx_bits = bits_for((uint64_t)L);
         NPGX_REQUIRE(idx_bits + key_bits <= 64, NPGX_ERR_RANGE, "FoundFragment sort key does not fit 64 bits");
         const TableArgs T = af_table_prepare(af, L, fills);
-        ti = af->timer.begin("table_insert", st, L * 8.0 + L * 12.0, L);
+        size_t ti = af->timer.begin("table_insert", st, L * 8.0 + L * 12.0, L);
         fills.add(af->segctr.p, (int64_t)A.nseg * 16 * 8, 0u);
         fills.launch(st);
         NPGX_HIP(hipGetLastError());
@@ -1250,180 +1420,159 @@ static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
         // the keys go where pass 1 collected (hseg, packed into hraw: both
         // hold every window of the run and are free since sort_unique)
         ti = af->timer.begin("ff_collect", st, local_windows * 0.375, local_windows);
-        hipLaunchKernelGGL(k_ff_collect, grid, block, 0, st, A, T, af->huniq.p, L, key_bits, af->hseg.p,
+        hipLaunchKernelGGL(k_ff_collect, grid(), dim3(WG), 0, st, A, T, af->huniq.p, L, key_bits, af->hseg.p,
                            af->segctr.p);
         NPGX_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_seg_compact, dim3((unsigned)A.nseg), dim3(256), 0, st, af->hseg.p, af->segctr.p,
                            A.nseg, A.seg_cap, af->hraw.p, af->counters.p + 2);
         NPGX_HIP(hipGetLastError());
         af->timer.end(ti, st);
-        NPGX_HIP(hipMemcpyAsync(hp, af->counters.p + 2, 8, hipMemcpyDeviceToHost, st));
+        NPGX_HIP(hipMemcpyAsync(hp + SLOT_N_KEYS, af->counters.p + 2, 8, hipMemcpyDeviceToHost, st));
         NPGX_HIP(stream_wait(st));
-        const uint64_t n_keys = hp[0];
-        const uint64_t keep = std::min<uint64_t>(n_keys, max_frag);
-        if (keep > 0) {
-            af->cand_sorted.ensure(n_keys);
-            size_t b4 = 0;
-            const unsigned end_bit = (unsigned)(idx_bits + key_bits);
-            NPGX_HIP(rocprim::radix_sort_keys(nullptr, b4, af->hraw.p, af->cand_sorted.p, (size_t)n_keys, 0u,
-                                              end_bit, st));
-            af->ensure_temp(b4);
-            ti = af->timer.begin("ff_sort", st, n_keys * 32.0, (int64_t)n_keys);
-            NPGX_HIP(rocprim::radix_sort_keys(af->temp.p, b4, af->hraw.p, af->cand_sorted.p, (size_t)n_keys, 0u,
-                                              end_bit, st));
-            af->timer.end(ti, st);
-            NPGX_HIP(hipMemcpyAsync(hp + 1, af->cand_sorted.p + (keep - 1), 8, hipMemcpyDeviceToHost, st));
-        }
-        if (af->defer_host && keep > 0) {  // the keys stay on the device (af_device_keys)
-            af->p_by_rank.assign(ss->by_rank.begin(), ss->by_rank.begin() + R);
-            // the rank table depends only on the sequence set: uploaded when it changes
-            if (!af->d_by_rank_valid || af->d_by_rank_host != af->p_by_rank) {
-                af->d_by_rank_valid = false;
-                af->d_by_rank.ensure((size_t)std::max<int32_t>(R, 1));
-                int32_t* hb = (int32_t*)af->pinned_dl.ensure((size_t)R / 2 + 2);
-                memcpy(hb, af->p_by_rank.data(), (size_t)R * 4);
-                NPGX_HIP(hipMemcpyAsync(af->d_by_rank.p, hb, (size_t)R * 4, hipMemcpyHostToDevice, st));
-                af->d_by_rank_host = af->p_by_rank;
-                af->d_by_rank_valid = true;
-            }
-            // the caller reads the keys on a stream of its own: they are complete when this returns
-            NPGX_HIP(stream_wait(st));
-            G = (hp[1] >> key_bits) + 1;
-            af->pending = true;
-            af->pending_used = true;
-            af->p_keep = (int64_t)keep;
-            af->p_G = G;
-            af->p_key_bits = key_bits;
-            af->p_k = k;
-            af->p_R = R;
-            af->p_meta.assign(meta.begin(), meta.begin() + R);
-            S.n_kept_groups = (int64_t)G;
-            S.n_blocks = S.n_fragments = -1;  // (af_materialize)
-            S.n_found_frags = -1;             // (npgx_af_stats_get)
-            af->found_pending = true;
-            af->f_A = A;
-            af->f_nchunks = nchunks;
-            af->f_windows = local_windows;
-            af->f_nH = nH;
-            af->has_result = true;
-            return;
-        }
-        // a plain run counts the FoundFragments of all of H now
-        af_found_total_enqueue(af, A, nchunks, local_windows, nH);
-        if (keep > 0) {
-            NPGX_HIP(stream_wait(st));
-            G = (hp[1] >> key_bits) + 1;
-            keys.resize(keep);
-            Hh.resize(G);
-            af->pinned_dl.ensure((keep + G) * 8);
-            uint64_t* pk = af->pinned_dl.p;
-            NPGX_HIP(hipMemcpyAsync(pk, af->cand_sorted.p, keep * 8, hipMemcpyDeviceToHost, st));
-            NPGX_HIP(hipMemcpyAsync(pk + keep, af->huniq.p, G * 8, hipMemcpyDeviceToHost, st));
-            NPGX_HIP(stream_wait(st));
-            memcpy(keys.data(), pk, keep * 8);
-            memcpy(Hh.data(), pk + keep, G * 8);
-        } else {
-            NPGX_HIP(stream_wait(st));
-        }
-        S.n_found_frags = (int64_t)hp[6];
-        S.n_kept_groups = (int64_t)G;
-    } else if (nH > 0) {
-        // --- sharded pass 2: FoundFragment counts per hash over the table of
-        // all of H, the cut from their scan, then the kept groups' windows
-        const TableArgs T = af_table_prepare(af, nH, fills);
-        af->counts.ensure((size_t)nH);
-        af->offsets.ensure((size_t)nH);
-        af->cursor.ensure((size_t)nH);
-        ti = af->timer.begin("table_insert", st, nH * 8.0 + nH * 12.0, nH);
-        fills.add(af->counts.p, nH * 4, 0u);
-        fills.add(af->cursor.p, nH * 4, 0u);
-        fills.launch(st);
-        NPGX_HIP(hipGetLastError());
-        af_table_insert(af, T, nH, st);
-        af->timer.end(ti, st);
-
-        // --- pass 2a: FoundFragment counts per hash
-        ti = af->timer.begin("ff_count", st, local_windows * (0.375 + 12.0), local_windows);
-        if (run_local) hipLaunchKernelGGL(k_ff_count, grid, block, 0, st, A, T, af->counts.p);
-        NPGX_HIP(hipGetLastError());
-        af->timer.end(ti, st);
-        // exchange 3: global FoundFragment count per hash; keep this rank's own
-        af->counts_local.ensure((size_t)nH);
-        af->offsets_local.ensure((size_t)nH);
-        NPGX_HIP(hipMemcpyAsync(af->counts_local.p, af->counts.p, (size_t)nH * 4, hipMemcpyDeviceToDevice, st));
-        NPGX_HIP(stream_wait(st));
-        comm_check(comm->allreduce_i32(comm->user, (int32_t*)af->counts.p, nH, NPGX_OP_SUM),
-                   "allreduce(counts, SUM)");
-        size_t b3 = 0;
-        NPGX_HIP(rocprim::exclusive_scan(nullptr, b3, af->counts.p, af->offsets.p, 0u, (size_t)nH,
-                                         rocprim::plus<uint32_t>(), st));
-        af->ensure_temp(b3);
-        ti = af->timer.begin("scan_cut", st, nH * 8.0, nH);
-        NPGX_HIP(rocprim::exclusive_scan(af->temp.p, b3, af->counts.p, af->offsets.p, 0u,
-                                         (size_t)nH, rocprim::plus<uint32_t>(), st));
-        af->cut.ensure(4);
-        hipLaunchKernelGGL(k_find_cut, dim3(1), dim3(64), 0, st, af->offsets.p, af->counts.p, nH,
-                           (uint64_t)af->opt.max_anchor_fragments, af->cut.p);
-        NPGX_HIP(hipGetLastError());
-        af->timer.end(ti, st);
-        NPGX_HIP(hipMemcpyAsync(hp, af->cut.p, 3 * 8, hipMemcpyDeviceToHost, st));
-        NPGX_HIP(stream_wait(st));
-        G = hp[0];
-        const uint64_t C = hp[1];
-        S.n_found_frags = (int64_t)hp[2];
-        S.n_kept_groups = (int64_t)G;
-        if (G > 0 && C > 0) {
-            const int idx_bits = bits_for(G);
-            NPGX_REQUIRE(idx_bits + key_bits <= 64, NPGX_ERR_RANGE,
-                         "FoundFragment sort key does not fit 64 bits");
-            // this rank scatters its own windows by its own offsets
-            NPGX_HIP(rocprim::exclusive_scan(af->temp.p, b3, af->counts_local.p, af->offsets_local.p,
-                                             0u, (size_t)nH, rocprim::plus<uint32_t>(), st));
-            hipLaunchKernelGGL(k_local_cut, dim3(1), dim3(64), 0, st, af->offsets_local.p,
-                               af->counts_local.p, nH, G, af->cut.p);
-            NPGX_HIP(hipGetLastError());
-            NPGX_HIP(hipMemcpyAsync(hp, af->cut.p + 3, 8, hipMemcpyDeviceToHost, st));
-            NPGX_HIP(stream_wait(st));
-            const uint64_t C_local = hp[0];
-            af->cand.ensure(std::max<uint64_t>(C_local, 1));
-            af->cand_sorted.ensure(C);
-            ti = af->timer.begin("ff_scatter", st, local_windows * 0.375 + C_local * 24.0, local_windows);
-            if (run_local && C_local > 0)
-                hipLaunchKernelGGL(k_ff_scatter, grid, block, 0, st, A, T, af->huniq.p, G, af->offsets_local.p,
-                                   af->cursor.p, key_bits, af->cand.p);
-            NPGX_HIP(hipGetLastError());
-            af->timer.end(ti, st);
-            // exchange 4: all ranks' FoundFragment keys of the kept groups
-            const int64_t tot = gather_u64(af->cand.p, (int64_t)C_local, "allgatherv(FoundFragments)");
-            NPGX_REQUIRE((uint64_t)tot == C, NPGX_ERR_STATE, "sharded FoundFragment count mismatch");
-            const uint64_t* sort_in = af->gathered.p;
-            size_t b4 = 0;
-            const unsigned end_bit = (unsigned)(idx_bits + key_bits);
-            NPGX_HIP(rocprim::radix_sort_keys(nullptr, b4, sort_in, af->cand_sorted.p, (size_t)C, 0u,
-                                              end_bit, st));
-            af->ensure_temp(b4);
-            ti = af->timer.begin("ff_sort", st, C * 32.0, (int64_t)C);
-            NPGX_HIP(rocprim::radix_sort_keys(af->temp.p, b4, sort_in, af->cand_sorted.p, (size_t)C,
-                                              0u, end_bit, st));
-            af->timer.end(ti, st);
-            const uint64_t keep = std::min<uint64_t>(C, (uint64_t)af->opt.max_anchor_fragments);
-            keys.resize(keep);
-            Hh.resize(G);
-            af->pinned_dl.ensure((keep + G) * 8);
-            uint64_t* pk = af->pinned_dl.p;
-            NPGX_HIP(hipMemcpyAsync(pk, af->cand_sorted.p, keep * 8, hipMemcpyDeviceToHost, st));
-            NPGX_HIP(hipMemcpyAsync(pk + keep, af->huniq.p, G * 8, hipMemcpyDeviceToHost, st));
-            NPGX_HIP(stream_wait(st));
-            memcpy(keys.data(), pk, keep * 8);
-            memcpy(Hh.data(), pk + keep, G * 8);
-        }
+        n_keys = hp[SLOT_N_KEYS];
+        keep = std::min<uint64_t>(n_keys, max_frag);
+        if (keep == 0) return;
+        af->cand_sorted.ensure(n_keys);
+        sort_keys(af, af->hraw.p, (size_t)n_keys, (unsigned)(idx_bits + key_bits), af->cand_sorted.p, "ff_sort",
+                  n_keys * 32.0);
+        NPGX_HIP(hipMemcpyAsync(hp + SLOT_LAST_KEY, af->cand_sorted.p + (keep - 1), 8, hipMemcpyDeviceToHost, st));
     }
 
-    h_dl = hms();
-    af_group_host(af, keys, Hh, key_bits, R, meta.data(), ss->by_rank.data(), k, true);
-    if (hdbg)
-        fprintf(stderr, "af host: prep %.3f ms, results downloaded at %.3f ms, grouping %.3f ms (%zu keys, %lld blocks)\n",
-                h_prep, h_dl, hms() - h_dl, keys.size(), (long long)S.n_blocks);
+    // The deferred result: the sorted keys stay on the device (af_device_keys)
+    // and `Pending` says how to group them later; the FoundFragment total is
+    // owed (`FoundOwed`).  Uploads the rank table when the sequence set changed
+    // and waits for the stream: the caller reads the keys on a stream of its own.
+    void defer() {
+        std::vector<int32_t> by_rank(ss->by_rank.begin(), ss->by_rank.begin() + R);
+        if (!af->d_by_rank_valid || af->d_by_rank_host != by_rank) {
+            af->d_by_rank_valid = false;
+            af->d_by_rank.ensure((size_t)std::max<int32_t>(R, 1));
+            int32_t* hb = (int32_t*)af->pinned_dl.ensure((size_t)R / 2 + 2);
+            memcpy(hb, by_rank.data(), (size_t)R * 4);
+            NPGX_HIP(hipMemcpyAsync(af->d_by_rank.p, hb, (size_t)R * 4, hipMemcpyHostToDevice, st));
+            af->d_by_rank_host = by_rank;
+            af->d_by_rank_valid = true;
+        }
+        NPGX_HIP(stream_wait(st));
+        G = (hp[SLOT_LAST_KEY] >> key_bits) + 1;
+        af->deferred = Pending{(int64_t)keep, G, key_bits, k, R, std::vector<SeqMeta>(meta.begin(), meta.begin() + R),
+                               std::move(by_rank)};
+        af->pending = true;
+        af->pending_used = true;
+        af->found_owed = FoundOwed{A, nchunks, local_windows, nH};
+        af->found_pending = true;
+        S.n_kept_groups = (int64_t)G;
+        S.n_blocks = S.n_fragments = -1;  // (af_materialize)
+        S.n_found_frags = -1;             // (af_found_pending)
+        af->has_result = true;
+    }
+
+    // A plain run on one GPU counts the FoundFragments of all of H now
+    // (enqueued behind the sort), waits, and downloads the kept keys and hashes
+    // (another wait)
+    void total_and_download() {
+        af_found_total_enqueue(af, FoundOwed{A, nchunks, local_windows, nH});
+        NPGX_HIP(stream_wait(st));
+        if (keep > 0) {
+            G = (hp[SLOT_LAST_KEY] >> key_bits) + 1;
+            download_keys(af, keep, G);
+        }
+        S.n_found_frags = (int64_t)hp[SLOT_CUT + CUT_TOTAL];
+        S.n_kept_groups = (int64_t)G;
+    }
+
+    // Sharded pass 2: FoundFragment counts per hash over the table of all of
+    // H, summed over the ranks (exchange 4; this rank's own kept), the cut from
+    // their scan (a wait), then the kept groups' windows (gather_kept)
+    void keys_sharded() {
+        af->cursor.ensure((size_t)nH);
+        fills.add(af->cursor.p, nH * 4, 0u);
+        const TableArgs T = count_and_cut(af, A, nchunks, local_windows, nH, fills, SLOT_SHARD_CUT, [&] {
+            af->counts_local.ensure((size_t)nH);
+            af->offsets_local.ensure((size_t)nH);
+            NPGX_HIP(hipMemcpyAsync(af->counts_local.p, af->counts.p, (size_t)nH * 4, hipMemcpyDeviceToDevice, st));
+            NPGX_HIP(stream_wait(st));
+            comm_check(comm->allreduce_i32(comm->user, (int32_t*)af->counts.p, nH, NPGX_OP_SUM),
+                       "allreduce(counts, SUM)");
+        });
+        NPGX_HIP(stream_wait(st));
+        G = hp[SLOT_SHARD_CUT + CUT_G];
+        const uint64_t C = hp[SLOT_SHARD_CUT + CUT_C];
+        S.n_found_frags = (int64_t)hp[SLOT_SHARD_CUT + CUT_TOTAL];
+        S.n_kept_groups = (int64_t)G;
+        if (G > 0 && C > 0) gather_kept(T, C);
+    }
+    // This rank scatters its own windows of the G kept groups by its own
+    // offsets (a wait for their count C_local), exchange 5 gathers all ranks'
+    // keys, C in all; sorted and downloaded (a wait)
+    void gather_kept(const TableArgs& T, uint64_t C) {
+        const int idx_bits = bits_for(G);
+        NPGX_REQUIRE(idx_bits + key_bits <= 64, NPGX_ERR_RANGE, "FoundFragment sort key does not fit 64 bits");
+        auto scan = scan_call(af, af->counts_local.p, af->offsets_local.p, nH);
+        size_t b = prim_temp(af, scan);
+        NPGX_HIP(scan((void*)af->temp.p, b));
+        hipLaunchKernelGGL(k_local_cut, dim3(1), dim3(64), 0, st, af->offsets_local.p, af->counts_local.p, nH, G,
+                           af->cut.p);
+        NPGX_HIP(hipGetLastError());
+        NPGX_HIP(hipMemcpyAsync(hp + SLOT_C_LOCAL, af->cut.p + 3, 8, hipMemcpyDeviceToHost, st));
+        NPGX_HIP(stream_wait(st));
+        const uint64_t C_local = hp[SLOT_C_LOCAL];
+        af->cand.ensure(std::max<uint64_t>(C_local, 1));
+        af->cand_sorted.ensure(C);
+        const size_t ti = af->timer.begin("ff_scatter", st, local_windows * 0.375 + C_local * 24.0, local_windows);
+        if (run_local && C_local > 0)
+            hipLaunchKernelGGL(k_ff_scatter, grid(), dim3(WG), 0, st, A, T, af->huniq.p, G, af->offsets_local.p,
+                               af->cursor.p, key_bits, af->cand.p);
+        NPGX_HIP(hipGetLastError());
+        af->timer.end(ti, st);
+        const int64_t tot = gather_u64(af->cand.p, (int64_t)C_local, "allgatherv(FoundFragments)");
+        NPGX_REQUIRE((uint64_t)tot == C, NPGX_ERR_STATE, "sharded FoundFragment count mismatch");
+        sort_keys(af, (const uint64_t*)af->gathered.p, (size_t)C, (unsigned)(idx_bits + key_bits), af->cand_sorted.p,
+                  "ff_sort", C * 32.0);
+        download_keys(af, std::min<uint64_t>(C, (uint64_t)af->opt.max_anchor_fragments), G);
+    }
+
+    // fragmenttg_postprocess on the host (af_group_host): the blocks and the used hashes
+    void group() {
+        static const bool hdbg = getenv("NPGX_AF_DEBUG") != nullptr;  // host phase times to stderr
+        h_dl = hms();
+        af_group_host(af, af->host_keys, af->host_H, key_bits, R, meta.data(), ss->by_rank.data(), k, true);
+        if (hdbg)
+            fprintf(stderr, "af host: prep %.3f ms, results downloaded at %.3f ms, grouping %.3f ms (%zu keys, %lld blocks)\n",
+                    h_prep, h_dl, hms() - h_dl, af->host_keys.size(), (long long)S.n_blocks);
+    }
+};
+
+static void af_run(npgx_af* af, const npgx_seqset* ss, const npgx_comm* comm) {
+    NPGX_REQUIRE(ss->device == af->device, NPGX_ERR_ARG, "sequence set and finder on different devices");
+    NPGX_HIP(hipSetDevice(af->device));
+    AfRun r(af, ss, comm);
+    r.drop_pending();
+    r.size_bloom();
+    r.layout();
+    if (r.nchunks_all == 0) {  // no window anywhere
+        r.empty_result();
+        return;
+    }
+    r.upload_layout();
+    r.kernel_args();
+    r.reset_pass1();
+    if (comm) r.exchange_bits();
+    r.bloom_pass();
+    r.pack_collected();
+    if (comm) r.exchange_boundary();
+    r.unique_hashes();
+    if (r.nH > 0 && !comm) {
+        r.keys_one_gpu();
+        if (af->defer_host && r.keep > 0) {  // the host result is deferred
+            r.defer();
+            return;
+        }
+        r.total_and_download();
+    } else if (r.nH > 0) {
+        r.keys_sharded();
+    }
+    r.group();  // (nothing collected or kept: the empty key list makes the empty result)
 }
 
 // fragmenttg_postprocess (AnchorFinder.cpp:356-391) on the truncated key list
@@ -1495,19 +1644,8 @@ static void af_group_host(npgx_af* af, const std::vector<uint64_t>& keys, const 
 
 // the deferred run's sorted keys and kept hashes -> host_keys / host_H
 static void af_download_pending(npgx_af* af) {
-    hipStream_t st = af->stream;
     NPGX_HIP(hipSetDevice(af->device));
-    std::vector<uint64_t>& keys = af->host_keys;
-    std::vector<uint64_t>& Hh = af->host_H;
-    keys.resize((size_t)af->p_keep);
-    Hh.resize((size_t)af->p_G);
-    af->pinned_dl.ensure((size_t)(af->p_keep + af->p_G) * 8 + 8);
-    uint64_t* pk = af->pinned_dl.p;
-    if (af->p_keep) NPGX_HIP(hipMemcpyAsync(pk, af->cand_sorted.p, (size_t)af->p_keep * 8, hipMemcpyDeviceToHost, st));
-    if (af->p_G) NPGX_HIP(hipMemcpyAsync(pk + af->p_keep, af->huniq.p, (size_t)af->p_G * 8, hipMemcpyDeviceToHost, st));
-    NPGX_HIP(stream_wait(st));
-    memcpy(keys.data(), pk, (size_t)af->p_keep * 8);
-    memcpy(Hh.data(), pk + af->p_keep, (size_t)af->p_G * 8);
+    download_keys(af, (uint64_t)af->deferred.keep, af->deferred.G);
 }
 
 // the deferred host result of the last run (see npgx_af.defer_host)
@@ -1516,8 +1654,9 @@ static void af_materialize(npgx_af* af) {
     af->pending = false;
     af_download_pending(af);
     af->regroups++;
-    af_group_host(af, af->host_keys, af->host_H, af->p_key_bits, af->p_R, af->p_meta.data(),
-                  af->p_by_rank.data(), af->p_k, af->pending_used);
+    const Pending& d = af->deferred;
+    af_group_host(af, af->host_keys, af->host_H, d.key_bits, d.R, d.meta.data(), d.by_rank.data(), d.k,
+                  af->pending_used);
 }
 
 // the used hashes of a deferred result that is not asked for (a second run
@@ -1527,7 +1666,7 @@ static void af_pending_used(npgx_af* af) {
     af_download_pending(af);
     const std::vector<uint64_t>& keys = af->host_keys;
     const std::vector<uint64_t>& Hh = af->host_H;
-    const int key_bits = af->p_key_bits;
+    const int key_bits = af->deferred.key_bits;
     const bool sort_used = !af->used.empty();
     const size_t nk = keys.size(), n0 = af->used.size();
     for (size_t i = 1; i < nk; i++) {
@@ -1544,9 +1683,9 @@ static void af_pending_used(npgx_af* af) {
 static void af_found_pending(npgx_af* af) {
     if (!af->found_pending) return;
     NPGX_HIP(hipSetDevice(af->device));
-    af_found_total_enqueue(af, af->f_A, af->f_nchunks, af->f_windows, af->f_nH);
+    af_found_total_enqueue(af, af->found_owed);
     NPGX_HIP(stream_wait(af->stream));
-    af->stats.n_found_frags = (int64_t)af->h_pinned[6];
+    af->stats.n_found_frags = (int64_t)af->h_pinned[SLOT_CUT + CUT_TOTAL];
     af->found_pending = false;
 }
 
@@ -1555,10 +1694,10 @@ void af_set_defer(npgx_af* af, bool on) { af->defer_host = on; }
 bool af_device_keys(npgx_af* af, AfDevKeys* o) {
     if (!af->pending) return false;
     o->keys = af->cand_sorted.p;
-    o->keep = af->p_keep;
-    o->key_bits = af->p_key_bits;
-    o->k = af->p_k;
-    o->R = af->p_R;
+    o->keep = af->deferred.keep;
+    o->key_bits = af->deferred.key_bits;
+    o->k = af->deferred.k;
+    o->R = af->deferred.R;
     o->meta = af->d_meta.p;
     o->by_rank = af->d_by_rank.p;
     return true;

@@ -80,6 +80,32 @@ CASES = [
     case("similar_off", genomes(19, 4, 500), {"similar_off", "inside"}, similar=False, maxf=200),
 ]
 
+# The sharded run alone (test_af_sharded_gpu.py).  SHARD_EXTRA: two sequences
+# of one chunk of 256 windows each, so that with three or five ranks some rank
+# owns no chunk and still joins every collective.  SHARDED is the part of
+# CASES the sharded run repeats, EPOCH_CASES two of them at the two Bloom
+# shapes (fp 0.1: 3 hash functions, window masks; fp 0.01: 7, none) for a
+# sharded pass 1 in three epochs.
+SHARD_EXTRA = [
+    case("two_short", genomes(21, 2, 250), set()),
+    case("two_short_off", genomes(21, 2, 250), {"similar_off"}, similar=False, maxf=30),
+]
+
+SHARDED = ("inside_group", "on_boundary", "max1", "max_is_total", "nothing_found", "shorter_than_k",
+           "singles_truncated", "used_set_kept", "n_runs", "k32", "similar_off")
+
+EPOCH_CASES = [dict(c, name="%s_fp%s" % (c["name"], fp), fp=fp)
+               for c in CASES if c["name"] in ("inside_group", "used_set_kept") for fp in ("0.1", "0.01")]
+EPOCH_HASHES = {"0.1": 3, "0.01": 7}
+
+WG = 256  # windows per chunk (anchor_finder.hip)
+
+
+def n_chunks(c):
+    """Chunks of the engine's window layout, from the sequence lengths and k."""
+    return sum((len(s) - c["k"] + 1 + WG - 1) // WG for s in c["seqs"] if len(s) >= c["k"])
+
+
 REQUIRED_TAGS = {"inside", "boundary", "max1", "max2", "untruncated", "max_is_total", "L_is_nH", "nothing", "empty",
                  "singles", "used", "used_cleared", "N", "palindrome", "k32", "similar_off"}
 

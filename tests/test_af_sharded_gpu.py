@@ -4,7 +4,9 @@ host staging (RCCL cannot put two ranks on one GPU; the product path binds
 the same callbacks to RCCL).  Every rank's result -- SoA anchors, |H|,
 FoundFragment count, the persistent used-hash set over two runs -- must equal
 the single-GPU npgx_af_run bit for bit, including truncation by
-max-anchor-fragments and anchor-similar=false."""
+max-anchor-fragments and anchor-similar=false.  The cut's edge cases
+(af_cut_cases.py), ranks that own no window and a pass 1 in several epochs
+run sharded against the oracle."""
 import os
 import socket
 
@@ -92,6 +94,83 @@ def test_sharded_equals_single(world, config, maxf, similar, staging):
             assert a["n_collected"] == b["n_collected"]
             assert a["n_found_frags"] == b["n_found_frags"]
             np.testing.assert_array_equal(a["used"], b["used"])
+
+
+def _cases_worker(rank, world, port, jobs, env, out):
+    """Every job (a case of af_cut_cases.py, its bloom-epochs, the oracle's
+    runs) on one process group.  A mismatch is recorded, not raised: the ranks
+    stay in step through the collectives of the later jobs."""
+    os.environ.update(env)  # (before the library loads)
+    import torch.distributed as dist
+    from npge_amd import _capi
+    from npge_amd.anchor_finder import AnchorFinder
+    from npge_amd.comm import TorchComm
+    from test_anchor_finder_gpu import _assert_same
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    _capi.check(_capi.lib().npgx_set_device(0))
+    comm = TorchComm(dist, staging="cpu")
+    bad = []
+    for c, epochs, oracle in jobs:
+        ss = _capi.SeqSet(c["seqs"], c["names"])
+        p = AnchorFinder(bloom_params=c["params"])
+        for key, v in (("anchor-size", c["k"]), ("anchor-fp", c["fp"]), ("anchor-similar", c["similar"]),
+                       ("max-anchor-fragments", c["maxf"]), ("bloom-seed", c["seed"]), ("bloom-epochs", epochs)):
+            p.set_opt_value(key, v)
+        for i, (clear, ro) in enumerate(zip(c["runs"], oracle)):
+            if clear:
+                p.clear_used()
+            r = p.find_sharded(ss, comm)
+            try:
+                _assert_same(r, ro, p.used_hashes())
+                assert p.stats.n_kept_groups == ro["kept_groups"], "n_kept_groups"
+            except AssertionError as e:
+                bad.append("%s run %d rank %d: %s" % (c["name"], i, rank, e))
+    out[rank] = bad
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _run_cases(world, jobs, env=None):
+    import af_cut_cases as cc
+    jobs = [(c, epochs, cc.oracle_runs(c)) for c, epochs in jobs]  # the oracle once, here
+    mgr = mp.Manager()
+    out = mgr.dict()
+    mp.spawn(_cases_worker, args=(world, _free_port(), jobs, env or {}, out), nprocs=world, join=True)
+    assert sorted(out.keys()) == list(range(world))
+    assert [b for r in range(world) for b in out[r]] == []
+    return jobs
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_sharded_cut_cases(world):
+    """The edges of the cut (af_cut_cases.py) on the sharded run, the only one
+    that cuts by count, scan and scatter: every rank's result, used hashes and
+    statistics are the oracle's.  BASE has 15 chunks at k = 12: two ranks split
+    inside sequence 1 (the `similar` rule across ranks), three on sequence starts."""
+    import af_cut_cases as cc
+    by = {c["name"]: c for c in cc.CASES}
+    jobs = _run_cases(world, [(by[n], 0) for n in cc.SHARDED])
+    assert any(ro["n_found_frags"] > ro["maxf"] for _, _, runs in jobs for ro in runs)
+
+
+@pytest.mark.parametrize("world", [3, 5])
+def test_sharded_rank_without_windows(world):
+    """Two chunks over three or five ranks: the ranks that own none still join
+    every collective, and all ranks end with the oracle's result."""
+    import af_cut_cases as cc
+    _run_cases(world, [(c, 0) for c in cc.SHARD_EXTRA])
+
+
+@pytest.mark.parametrize("fuse", ["1", "0"])
+def test_sharded_epochs(fuse):
+    """A sharded pass 1 in three epochs: the lower ranks' bits (P0) under every
+    epoch, the range's first window reported by the first epoch alone and its
+    last by the last, with the window masks (fp 0.1; fused launches or not) and
+    without them (fp 0.01)."""
+    import af_cut_cases as cc
+    _run_cases(2, [(c, 3) for c in cc.EPOCH_CASES], env={"NPGX_AF_EPOCH_FUSE": fuse})
 
 
 def _bb_worker(rank, world, port, config, out, loop=False):
